@@ -20,21 +20,38 @@ rebuilds its own 4096 blocks (block-index partition; BASELINE.json C4 at N=8):
 weak scaling.  The barrier and the max-over-ranks run over gloo on the host;
 nothing crosses GPUs (no RCCL).
 
-Printed JSON line (rank 0): the contract fields plus
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K
+steps, writes its outputs if --dump-outputs is given and prints the line:
+nothing else.  --full adds every other leg below (each can be turned off
+again with its --no-* flag); they all run after the timed steps.
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed
+(the parity the encode wrote, the shards the rebuild wrote) goes to
+DIR/<name>.npy (dump_outputs).  The inputs depend on the arguments alone
+(SEED), so two builds run with the same arguments can be compared output
+for output.
+
+Printed JSON line (rank 0): the contract fields (ms_per_step: wall
+milliseconds of one timed step) plus
   encode / rebuild : per-direction GiB/s, kernel ms and roofline fraction
   roofline         : the encode kernel (C2, the north-star target): its
                      algorithmic bytes per launch (k+m)*S*n / its average
-                     HIP-event duration, vs 8 TB/s; roofline_rebuild likewise;
-                     `traffic` from rocprofv3 counter passes this run makes
-                     (pmc_traffic)
+                     HIP-event duration, vs 8 TB/s; roofline_rebuild likewise
   ranks            : per-GPU GiB/s, node sum (C4's wording)
+  build_id         : memo_ec_build_id() of the loaded library (== SHA-256 of
+                     the sources in this tree: build_matches_sources)
+and with --full
+  roofline.traffic : from rocprofv3 counter passes this run makes
+                     (pmc_traffic); roofline.achievable from the stream probe
+  oracle_parity    : whole-batch comparison with the CPU oracle;
+                     rebuild.round_trip_bit_exact: the rebuilt shards against
+                     the original ones, on the device
+  rebuild_small, c5_mixed, c1, sha256, plugin, sweep (--sweep)
   cpu_baseline     : the C port (oracle/, test infrastructure) timed on this
                      host's CPU share on a bounded sample (rank 0, every N,
                      after the timed steps)
   end_to_end       : pinned host -> HBM -> host rate (PCIe-inclusive; not
                      `value`), every rank over its own link, node sum at N>1
-  build_id         : memo_ec_build_id() of the loaded library (== SHA-256 of
-                     the sources in this tree: build_matches_sources)
 """
 import argparse
 import json
@@ -66,6 +83,12 @@ def parse(argv=None):
     ap.add_argument("--block-bytes", type=int, default=1 << 20)
     ap.add_argument("--blocks", type=int, default=4096, help="blocks per GPU")
     ap.add_argument("--erasures", type=int, default=4)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side leg (stream probe, oracle "
+                         "comparisons, CPU baseline, end-to-end, counter passes, 4 KiB, C5, plugin "
+                         "and SHA-256 lines); the --no-* flags and --sweep act on a --full run")
     ap.add_argument("--no-small", action="store_true", help="skip the 4 KiB random-rebuild lines")
     ap.add_argument("--small-only", action="store_true",
                     help=argparse.SUPPRESS)  # the counter pass child of pmc_small: 4 KiB lines only
@@ -1131,7 +1154,7 @@ def check_devices(rows, same_device):
             seen[i[key]] = r["rank"]
 
 
-# Legs of the default line that run at N = 1 only (single-GPU workloads, or
+# Legs of the --full line that run at N = 1 only (single-GPU workloads, or
 # host-side lines that do not depend on N): named in the N > 1 line itself.
 N1_ONLY_LEGS = [("rebuild_small", "no_small", "1,048,576 x 4 KiB rebuilds: a single-GPU workload"),
                 ("c5_mixed", "no_c5", "BASELINE.json C5 is quoted on 1 GPU"),
@@ -1140,10 +1163,17 @@ N1_ONLY_LEGS = [("rebuild_small", "no_small", "1,048,576 x 4 KiB rebuilds: a sin
                 ("sweep", None, "BASELINE.json C5 sweep is quoted on 1 GPU (--sweep)")]
 
 
+def runs(args, no_flag):
+    """True when a side leg runs: --full asked for them and the leg's own
+    --no-* flag did not turn it off again."""
+    return args.full and not getattr(args, no_flag)
+
+
 def skipped_at_n(args, world):
-    """{leg: reason} of the legs an N > 1 line leaves out (empty at N = 1);
-    legs the run's flags turned off are not listed."""
-    if world <= 1:
+    """{leg: reason} of the legs a --full N > 1 line leaves out (empty at
+    N = 1 and for a plain run, which has no side legs); legs the run's flags
+    turned off are not listed."""
+    if world <= 1 or not args.full:
         return {}
     out = {}
     for leg, flag, why in N1_ONLY_LEGS:
@@ -1168,8 +1198,8 @@ POST_RATES = {"oracle_core_GiBs": 27.0, "dtoh_GiBs": 20.0, "pmc_pass_s": 60.0, "
 
 
 def post_timed_seconds(args, world, threads_per_rank, S, rates=POST_RATES):
-    """Estimated seconds a rank spends outside the timed steps at `world`
-    ranks with `threads_per_rank` CPU threads each (main: the job's CPU share
+    """Estimated seconds a rank of a --full run spends outside the timed
+    steps at `world` ranks with `threads_per_rank` CPU threads each (main: the job's CPU share
     split over the ranks): start-up (torch import, inputs), the stream probe,
     the whole-batch oracle checks of its own C2 / C3 batches (staged over its
     own link, recomputed on its threads), the PCIe end-to-end leg, and on
@@ -1245,8 +1275,9 @@ def assemble(args, world, rows, wall_max, S):
         rb_alg = (k + e) * S * n
         res["encode"].pop("value")
         res["rebuild"] = {"GiBs_kernel": round(n * B / (reb["kernel_ms_avg"] * 1e-3) / 2**30, 1),
-                          "bytes_per_launch": rb_alg, "round_trip_bit_exact": all(
-                              r["rebuild_bit_exact"] for r in rows), **reb}
+                          "bytes_per_launch": rb_alg, **reb}
+        if all("rebuild_bit_exact" in r for r in rows):  # checked by --full runs
+            res["rebuild"]["round_trip_bit_exact"] = all(r["rebuild_bit_exact"] for r in rows)
         res["roofline_rebuild"] = {"bound": "hbm", "kernel": r0["rebuild_kernel"],
                                    "achieved": reb["achieved"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
                                    "frac": reb["frac"], "traffic": None, "bytes_per_launch": rb_alg,
@@ -1273,6 +1304,35 @@ def assemble(args, world, rows, wall_max, S):
     if world > 1:
         res["skipped_at_n"] = skipped_at_n(args, world)
     return res
+
+
+DUMP_SAMPLE = 4 << 20  # bytes sampled per output: 16 MiB of float32 each
+
+
+def dump_outputs(torch, dirname, outputs, tag=""):
+    """--dump-outputs: the arrays the last timed step left behind, as .npy
+    files in `dirname`.  `outputs` is [(name, uint8 device tensor (n, r * S),
+    r)].  Per output, two files (`tag` names the rank at N > 1):
+      <name>.npy             float32: every byte in row-major order when there
+                             are at most DUMP_SAMPLE of them, else the bytes at
+                             DUMP_SAMPLE positions drawn once from
+                             default_rng(SEED) over the flat index range (a
+                             function of the shape alone, sorted);
+      <name>_shard_sums.npy  float64 (n, r): the byte sum of every shard, so
+                             every byte of the output weighs in (exact:
+                             S * 255 < 2**53).
+    4096 x 1 MiB blocks with m = e = 4: 2 x 16 MiB + 2 x 128 KiB."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t, r in outputs:
+        flat = t.reshape(-1)
+        total = flat.numel()
+        if total > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(SEED).integers(0, total, size=DUMP_SAMPLE, dtype=np.int64))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        np.save(os.path.join(dirname, "%s%s.npy" % (name, tag)), flat.cpu().numpy().astype(np.float32))
+        sums = t.reshape(t.shape[0], r, -1).sum(dim=2, dtype=torch.int64)
+        np.save(os.path.join(dirname, "%s_shard_sums%s.npy" % (name, tag)),
+                sums.cpu().numpy().astype(np.float64))
 
 
 def main():
@@ -1345,8 +1405,9 @@ def main():
         surv = torch.empty((n, k * S), dtype=torch.uint8, device="cuda")
         codec.gather_shards(k, m, S, n, data, par, sd, surv)
         out = torch.empty((n, e * S), dtype=torch.uint8, device="cuda")
-        want = torch.empty((n, e * S), dtype=torch.uint8, device="cuda")
-        codec.gather_shards(k, m, S, n, data, par, ld, want)
+        if args.full:  # the original shards, to compare the rebuilt ones with
+            want = torch.empty((n, e * S), dtype=torch.uint8, device="cuda")
+            codec.gather_shards(k, m, S, n, data, par, ld, want)
         fns.append(lambda: codec.rebuild(k, m, sd, surv, ld, out))
     torch.cuda.synchronize()
 
@@ -1360,9 +1421,10 @@ def main():
            "encode": kstats(kms[0], (k + m) * S * n)}
     if e > 0:
         row["rebuild"] = kstats(kms[1], (k + e) * S * n)
-        row["rebuild_bit_exact"] = bool(torch.equal(out, want))
         row["rebuild_kernel"] = codec.rebuild_kernel_name(n, k, S, e)
-        del want
+        if args.full:
+            row["rebuild_bit_exact"] = bool(torch.equal(out, want))
+            del want
     rows = [row]
     wall_max = wall
     if dist is not None:
@@ -1373,27 +1435,35 @@ def main():
         wall_max = float(t.item())
     result = assemble(args, world, rows, wall_max, S)
 
-    if args.no_pmc:
+    if not runs(args, "no_pmc"):
         for key in ("roofline", "roofline_rebuild"):
             if key in result:
-                result[key]["traffic_note"] = "not measured (--no-pmc)"
+                result[key]["traffic_note"] = ("not measured (--no-pmc)" if args.full else
+                                               "not measured (counter passes run with --full)")
     result["build_id"] = ec.build_id()
     result["build_matches_sources"] = result["build_id"] == ec.source_id()
+    result["full"] = args.full
 
-    # ---- after the timed steps and their closing barrier: the baselines,
-    # checks and side measurements, at every N.  Every rank measures its own
-    # GPU (the achievable rate of the encode's traffic, PCIe end-to-end rate
-    # over its own link) and compares its own whole batch with the CPU
-    # oracle, concurrently; rank 0 alone times the CPU baseline and the
-    # counter passes while the others wait at the final barrier.
+    if args.dump_outputs:
+        outputs = [("parity", par, m)] + ([("rebuilt", out, e)] if e > 0 else [])
+        dump_outputs(torch, args.dump_outputs, outputs, "" if world == 1 else "_rank%d" % rank)
+
+    # ---- --full, after the timed steps and their closing barrier: the
+    # baselines, checks and side measurements, at every N.  Every rank
+    # measures its own GPU (the achievable rate of the encode's traffic, PCIe
+    # end-to-end rate over its own link) and compares its own whole batch
+    # with the CPU oracle, concurrently; rank 0 alone times the CPU baseline
+    # and the counter passes while the others wait at the final barrier.
     extra = {}
-    # What the memory system allows for this exact traffic (SURVEY.md 8(d)'s
-    # "measured" reference): the encode's tiles and loads/stores, no GF math.
-    scratch = torch.empty_like(par)
-    extra["probe"] = probe_rate(torch, codec, stream, k, m, data, scratch)
-    del scratch
+    if args.full:
+        # What the memory system allows for this exact traffic (SURVEY.md
+        # 8(d)'s "measured" reference): the encode's tiles and loads/stores,
+        # no GF math.
+        scratch = torch.empty_like(par)
+        extra["probe"] = probe_rate(torch, codec, stream, k, m, data, scratch)
+        del scratch
     vthreads = max(1, cpu_threads(world) // world)
-    if not args.no_verify:
+    if runs(args, "no_verify"):
         # Whole-batch parity with the CPU oracle (oracle/rs_simd.c): every
         # parity byte of the timed encode (C2) and every shard the timed
         # rebuild produced (C3, this batch's path), on this rank's blocks.
@@ -1407,54 +1477,55 @@ def main():
         del stage
     if e > 0:
         del surv, out
-    if not args.no_e2e:
+    if runs(args, "no_e2e"):
         if dist is not None:
             dist.barrier()  # all links busy at once, as on a node serving every GPU
         extra["e2e"], extra["lat"] = end_to_end(torch, ec, codec, data, par, k, m, B, n)
         codec.set_stream(stream)
     extras = [extra]
-    if dist is not None:
+    if dist is not None and args.full:
         extras = [None] * world
         dist.all_gather_object(extras, extra)
     merge_extras(result, extras)
-    log("rank %d: timed steps done, side measurements" % rank)
+    if args.full:
+        log("rank %d: timed steps done, side measurements" % rank)
     checks = [v["bit_exact"] for v in result.get("oracle_parity", {}).values()]
-    if world == 1:
+    if world == 1 and args.full:
         stage = None if args.no_verify else HostStage(torch)
-        if not args.no_small:
+        if runs(args, "no_small"):
             result["rebuild_small"] = rebuild_small(torch, ec, codec, stream, args.steps, args.warmup,
                                                     args.settle_ms, stage, vthreads)
             for v in result["rebuild_small"].values():
                 checks += [v["bit_exact"], v["uniform_pattern"]["bit_exact"]]
                 if "oracle" in v:
                     checks.append(v["oracle"]["bit_exact"])
-        if not args.no_c5:
+        if runs(args, "no_c5"):
             result["c5_mixed"] = c5_mixed(torch, ec, codec, stream, args.c5_gib, args.steps,
                                           args.warmup, args.settle_ms, stage, vthreads)
             checks.append(result["c5_mixed"]["round_trip_bit_exact"])
             if "oracle_bit_exact" in result["c5_mixed"]:
                 checks.append(result["c5_mixed"]["oracle_bit_exact"])
         del stage
-    if not args.no_verify:
+    if runs(args, "no_verify"):
         result["oracle_bit_exact"] = bool(checks) and all(checks)
     if rank == 0:
-        if not args.no_cpu:
+        if runs(args, "no_cpu"):
             log("cpu baseline")
             result["cpu_baseline"] = cpu_baseline(k, m, B, S, args.cpu_seconds, par[:4].cpu().numpy(),
                                                   world)
             result["c1"] = c1_case(torch, ec, codec, stream, world)
-        if not args.no_pmc:
+        if runs(args, "no_pmc"):
             log("counter passes")
             pmc_traffic(args, result, local, world)
             if "rebuild_small" in result:
                 pmc_small(args, result, local, world)
-        if not args.no_plugin and world == 1:
+        if runs(args, "no_plugin") and world == 1:
             log("plugin lines")
             result["plugin"] = plugin_lines()
-        if not args.no_sha and world == 1:
+        if runs(args, "no_sha") and world == 1:
             log("sha-256 lines")
             result["sha256"] = sha_lines(torch, codec, stream, data, n, B, cpu_threads(world))
-        if args.sweep and world == 1:
+        if args.full and args.sweep and world == 1:
             del data, par
             result["sweep"] = sweep(torch, ec, codec, stream, args.sweep_gib, max(3, args.steps // 4),
                                     args.warmup, args.settle_ms, cpu=not args.no_cpu)

@@ -175,7 +175,7 @@ def test_bench_assemble_world_8_c4_line():
     distinct device identities give distinct_devices 8, 32768 global blocks
     (4096 per GPU), and the line names the N = 1-only legs it left out."""
     import bench
-    args = bench.parse(["--gpus", "8", "--steps", "10"])
+    args = bench.parse(["--gpus", "8", "--steps", "10", "--full"])
     S = 104896
     n, B, K = args.blocks, args.block_bytes, 10
     assert (n, B) == (4096, 1 << 20)
@@ -193,7 +193,7 @@ def test_bench_assemble_world_8_c4_line():
     assert set(res["skipped_at_n"]) == {"rebuild_small", "c5_mixed", "plugin", "sha256"}
     assert res["value"] == round(8 * n * B * 2 * K / 0.021 / 2**30, 3)
     # flags that turn a leg off leave it out of the list; N = 1 lists none
-    quiet = bench.parse(["--gpus", "8", "--no-plugin", "--no-sha", "--sweep"])
+    quiet = bench.parse(["--gpus", "8", "--full", "--no-plugin", "--no-sha", "--sweep"])
     assert set(bench.skipped_at_n(quiet, 8)) == {"rebuild_small", "c5_mixed", "sweep"}
     one = bench.parse(["--gpus", "1"])
     assert bench.skipped_at_n(one, 1) == {}
@@ -216,7 +216,7 @@ def test_world_8_line_fits_the_rank_lease(monkeypatch):
     monkeypatch.setattr(bench, "host_cores", lambda: 256)
     monkeypatch.setattr(bench, "_cgroup_cpus", lambda: 16)
     monkeypatch.delenv("OMP_NUM_THREADS", raising=False)
-    args = bench.parse(["--gpus", "8"])
+    args = bench.parse(["--gpus", "8", "--full"])
     world, S = 8, 104896
     per_rank = max(1, bench.cpu_threads(world) // world)   # what main() gives each rank's checks
     assert per_rank == 2
@@ -229,7 +229,7 @@ def test_world_8_line_fits_the_rank_lease(monkeypatch):
     # one thread per rank (a 8-CPU share) still fits; the N = 1 line, with
     # every leg, fits its own lease on the box's 16 threads
     assert bench.post_timed_seconds(args, world, 1, S)["rank0"] + timed < args.rank_timeout
-    one = bench.parse(["--gpus", "1"])
+    one = bench.parse(["--gpus", "1", "--full"])
     assert bench.post_timed_seconds(one, 1, 16, S)["rank0"] + timed < one.rank_timeout
     # a slower box (half the rates, twice the pass times) still fits at N = 8
     slow = {k: (v / 2 if k.endswith("GiBs") else v * 2) for k, v in bench.POST_RATES.items()}
@@ -314,7 +314,7 @@ def _bench_json(r):
 
 
 BENCH_SMALL = ["--gpus", "2", "--same-device", "--steps", "3", "--warmup", "2", "--settle-ms", "0",
-               "--blocks", "64", "--no-cpu", "--no-e2e", "--no-small", "--no-pmc"]
+               "--blocks", "64", "--full", "--no-cpu", "--no-e2e", "--no-small", "--no-pmc"]
 
 
 @pytest.mark.gpu
@@ -353,14 +353,14 @@ def test_bench_two_ranks_under_torchrun():
 @pytest.mark.gpu
 @pytest.mark.timeout(400)
 def test_bench_n2_line_is_self_sufficient():
-    """At N = 2 the line still carries the CPU baseline (rank 0, after the
+    """At N = 2 the --full line still carries the CPU baseline (rank 0, after the
     timed steps), every rank's PCIe end-to-end rate and their sum, the
     counter-measured traffic of this run, and the loaded library's build id
     (== the sources' hash)."""
     import subprocess
     import sys
     args = ["--gpus", "2", "--same-device", "--steps", "3", "--warmup", "2", "--settle-ms", "0",
-            "--blocks", "256", "--no-small", "--cpu-seconds", "1"]
+            "--blocks", "256", "--full", "--no-small", "--cpu-seconds", "1"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args,
                        capture_output=True, text=True, timeout=380, cwd=ROOT)
     res = _bench_json(r)
@@ -484,15 +484,15 @@ def test_whole_batch_checks_catch_one_byte():
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 def test_bench_default_line_runs_every_leg():
-    """The driver's own command shape at N = 1 (fewer steps, a short CPU
-    sample): the line carries the whole-batch oracle comparison of C2, C3,
+    """The --full run at N = 1 (fewer steps, a short CPU sample): the line
+    carries the whole-batch oracle comparison of C2, C3,
     the 4 KiB rebuilds and C5, the achievable-rate probe, the 4 KiB counter
     summary, counter traffic, the CPU baseline, the device identity, the
     SHA-256 lines and the plugin-level lines."""
     import subprocess
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5",
-                        "--warmup", "2", "--cpu-seconds", "1"],
+                        "--warmup", "2", "--full", "--cpu-seconds", "1"],
                        capture_output=True, text=True, timeout=560, cwd=ROOT)
     res = _bench_json(r)
     assert res["oracle_bit_exact"] is True
@@ -569,3 +569,88 @@ def test_sha_digest_check_catches_one_flipped_byte():
     digs[17, 3] ^= 1
     assert not bench.sha_digests_ok(msgs, digs, range(40), 257, 4)
     assert bench.sha_digests_ok(msgs, digs, range(17), 257, 1)
+
+
+def test_plain_run_has_no_side_legs():
+    """Without --full no side leg runs, whatever the --no-* flags say; with
+    --full each runs unless its own flag turns it off; a plain N > 1 line
+    lists no legs as skipped (it has none)."""
+    import bench
+    legs = ("no_small", "no_cpu", "no_e2e", "no_pmc", "no_verify", "no_c5", "no_plugin", "no_sha")
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not plain.full and plain.dump_outputs is None and (plain.steps, plain.warmup) == (7, 3)
+    assert not any(bench.runs(plain, leg) for leg in legs)
+    full = bench.parse(["--gpus", "1", "--full", "--no-pmc"])
+    assert [leg for leg in legs if not bench.runs(full, leg)] == ["no_pmc"]
+    assert bench.skipped_at_n(bench.parse(["--gpus", "8"]), 8) == {}
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files: a small output
+    whole, a large one at fixed positions (the same on every call), and the
+    byte sum of every shard (CPU tensors stand in for device ones)."""
+    import torch
+    import bench
+    rng = np.random.default_rng(SEED)
+    small = rng.integers(0, 256, size=(5, 3 * 64), dtype=np.uint8)
+    big = rng.integers(0, 256, size=(9, 2 * 1000), dtype=np.uint8)
+    old, bench.DUMP_SAMPLE = bench.DUMP_SAMPLE, 4096
+    try:
+        for d in ("a", "b"):
+            bench.dump_outputs(torch, str(tmp_path / d), [("parity", torch.from_numpy(small), 3),
+                                                          ("rebuilt", torch.from_numpy(big), 2)])
+    finally:
+        bench.DUMP_SAMPLE = old
+    got = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["parity.npy", "parity_shard_sums.npy", "rebuilt.npy", "rebuilt_shard_sums.npy"]
+    assert got["parity.npy"].dtype == np.float32 and got["parity_shard_sums.npy"].dtype == np.float64
+    assert np.array_equal(got["parity.npy"], small.reshape(-1).astype(np.float32))
+    assert np.array_equal(got["parity_shard_sums.npy"], small.reshape(5, 3, 64).sum(axis=2))
+    assert got["rebuilt.npy"].shape == (4096,)
+    pos = np.sort(np.random.default_rng(SEED).integers(0, big.size, size=4096, dtype=np.int64))
+    assert np.array_equal(got["rebuilt.npy"], big.reshape(-1)[pos].astype(np.float32))
+    assert np.array_equal(got["rebuilt_shard_sums.npy"], big.reshape(9, 2, 1000).sum(axis=2))
+    for name, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / name))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_outputs(tmp_path, O):
+    """A plain run times exactly --steps steps, prints the contract fields
+    and no side leg, and --dump-outputs leaves the last step's parity and
+    rebuilt shards: equal to the CPU oracle's for the same arguments."""
+    import subprocess
+    import sys
+    import bench
+    k, m, B, n, e = 10, 4, 1 << 16, 48, 4
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                        "--warmup", "2", "--settle-ms", "0", "--blocks", str(n), "--block-bytes", str(B),
+                        "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=120, cwd=ROOT)
+    res = _bench_json(r)
+    assert res["steps"] == 3 and res["warmup"] == 2 and res["warmup_steps_run"] == 2
+    assert len(res["encode"]["kernel_ms_first_last"]) == 2 and res["ms_per_step"] > 0
+    # value and ms_per_step are one wall time: equal up to their rounding
+    # (ms_per_step to 4 decimals, value to 3)
+    assert res["value"] == pytest.approx(2 * n * B / (res["ms_per_step"] * 1e-3) / 2**30,
+                                         rel=1e-4 / res["ms_per_step"], abs=1e-3)
+    assert (res["unit"], res["higher_is_better"], res["dtype"]) == ("GiB/s", True, "u8")
+    assert res["full"] is False and res["build_matches_sources"]
+    for leg in ("cpu_baseline", "c1", "oracle_parity", "oracle_bit_exact", "end_to_end", "rebuild_small",
+                "c5_mixed", "plugin", "sha256", "sweep"):
+        assert leg not in res
+    assert "achievable" not in res["roofline"] and res["roofline"]["traffic"] is None
+    assert "round_trip_bit_exact" not in res["rebuild"]
+    S = O.shard_size(B, k)
+    data = O.fill_blocks(SEED, 0, n, B, k, S)
+    par = O.encode(k, m, S, data)
+    _, l_idx = O.erasures(SEED, 0, n, k, m, e)
+    lost = O.gather(k, m, S, data, par, l_idx)
+    for name, want, r_ in (("parity", par, m), ("rebuilt", lost, e)):
+        got = np.load(tmp_path / "out" / ("%s.npy" % name))
+        assert got.dtype == np.float32 and got.nbytes <= 32 << 20
+        pos = np.sort(np.random.default_rng(SEED).integers(0, want.size, size=bench.DUMP_SAMPLE, dtype=np.int64))
+        ref = want.reshape(-1)[pos] if want.size > bench.DUMP_SAMPLE else want.reshape(-1)
+        assert np.array_equal(got, ref.astype(np.float32)), name
+        sums = np.load(tmp_path / "out" / ("%s_shard_sums.npy" % name))
+        assert np.array_equal(sums, want.reshape(n, r_, S).sum(axis=2, dtype=np.int64)), name

@@ -18,8 +18,8 @@ for p in $PROBES; do
   case $p in
     image_ab) timeout -k 10 600 python -u tools/image_ab.py ${AB_ROUNDS:-3} 10 $AB_SHAPES > $OUT/image_ab.jsonl 2> $OUT/image_ab.err ;;
     host) timeout -k 10 300 host/_build/test_erasure > $OUT/host_tests.log 2>&1 ;;
-    bench) timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err ;;
-    sweep) timeout -k 10 900 python bench.py --sweep --no-pmc --no-plugin --no-sha > $OUT/sweep.json 2> $OUT/sweep.err ;;
+    bench) timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err ;;
+    sweep) timeout -k 10 900 python bench.py --full --sweep --no-pmc --no-plugin --no-sha > $OUT/sweep.json 2> $OUT/sweep.err ;;
     profile) OUT=$OUT/prof bash tools/profile.sh > $OUT/profile.log 2>&1 ;;
     pmc4k) OUT=$OUT/pmc_4k bash tools/pmc_4k.sh > $OUT/pmc_4k.log 2>&1 ;;
     pmc1t) OUT=$OUT/pmc_onetile bash tools/pmc_onetile.sh > $OUT/pmc_onetile.log 2>&1 ;;
