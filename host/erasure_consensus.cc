@@ -160,6 +160,18 @@ void Codec::encode(int k, int m, size_t S, size_t n, const uint8_t* data, uint8_
   ++encode_calls_;
 }
 
+void Codec::verify(int k, int m, size_t S, size_t n, const uint8_t* data, const uint8_t* parity,
+                   uint32_t* verdict, bool pinned) {
+  split(n, [&](size_t d, size_t b0, size_t cnt) {
+    auto* c = acquire(d);
+    const int rc = memo_ec_verify_batch(c, k, m, S, cnt, data + b0 * k * S, parity + b0 * m * S,
+                                        verdict + b0, pinned ? MEMO_EC_HOST_PINNED : MEMO_EC_HOST);
+    release(d, c);
+    return rc;
+  }, "verify");
+  ++verify_calls_;
+}
+
 void Codec::rebuild(int k, int m, size_t S, size_t n, const uint8_t* surv_idx,
                     const uint8_t* surv, const uint8_t* lost_idx, int e, uint8_t* out, bool pinned) {
   split(n, [&](size_t d, size_t b0, size_t cnt) {
@@ -646,7 +658,11 @@ std::string ErasureConsensus::stats_text() const {
                   {"corrupt_shards_rewritten", std::to_string(corrupt_rewritten_)},
                   {"pending_evictions", std::to_string(pending_evictions())},
                   {"encode_calls", std::to_string(codec_.encode_calls())},
-                  {"rebuild_calls", std::to_string(codec_.rebuild_calls())}});
+                  {"rebuild_calls", std::to_string(codec_.rebuild_calls())},
+                  {"scrubbed_blocks", std::to_string(scrubbed_blocks_)},
+                  {"scrub_mismatches", std::to_string(scrub_mismatches_)},
+                  {"scrub_shards_rewritten", std::to_string(scrub_rewritten_)},
+                  {"scrub_unrecoverable", std::to_string(scrub_unrecoverable_)}});
 }
 
 Buffer ErasureConsensus::padded(const Block& b, size_t S) const {
@@ -1410,19 +1426,48 @@ std::vector<std::vector<int>> retry_subsets(int n, int k, int limit) {
 // reachable shard is fetched, k-subsets are decoded until one reassembles to
 // the address (at most verify_subsets), and each shard in hand that
 // disagrees with the verified block is rewritten on its holder.
-std::unique_ptr<Block> ErasureConsensus::recover(const Address& a, bool parallel) {
+std::unique_ptr<Block> ErasureConsensus::recover(const Address& a, bool parallel, size_t* rewritten) {
   const int k = o_.k, m = o_.m, total = k + m;
   // k + 1 shards first (one spare out-votes one wrong shard, and a holder
   // that is down does not send the gather over the whole membership), all
   // of them when that finds no good subset
   if (k + 1 < total)
-    if (auto b = recover_from(a, k + 1, parallel)) return b;
-  if (auto b = recover_from(a, total, parallel)) return b;
+    if (auto b = recover_from(a, k + 1, parallel, rewritten)) return b;
+  if (auto b = recover_from(a, total, parallel, rewritten)) return b;
   throw AddressMismatch("erasure: reassembled block does not match its address (no k-subset of the "
                         "reachable shards matches)");
 }
 
-std::unique_ptr<Block> ErasureConsensus::recover_from(const Address& a, int want, bool parallel) {
+// `padded_block` (k x S) is the verified block of `a`: every shard in `have`
+// (index, wire bytes) that differs from its re-encoding is rewritten on the
+// holder that served it (from[index]).  Returns the shards rewritten.
+size_t ErasureConsensus::rewrite_disagreeing(const Address& a, const ShardHeader& h,
+                                             const Buffer& padded_block,
+                                             const std::vector<std::pair<int, Buffer>>& have,
+                                             const std::vector<Node*>& from) {
+  const int k = o_.k, m = o_.m;
+  const size_t S = h.shard_size;
+  Buffer parity((size_t)m * S);
+  codec_.encode(k, m, S, 1, padded_block.data(), parity.data());
+  const ShardKeys keys(a);
+  size_t n = 0;
+  for (const auto& sh : have) {
+    const int i = sh.first;
+    const uint8_t* want = i < k ? padded_block.data() + (size_t)i * S : parity.data() + (size_t)(i - k) * S;
+    if (std::memcmp(sh.second.data() + ShardHeader::kSize, want, S) == 0 || !from[i]) continue;
+    try {
+      from[i]->store(keys(i), encode_shard(h, want, i));
+      ++corrupt_rewritten_;
+      ++n;
+    } catch (Error&) {
+      // unreachable now: the next fetch or repair meets it again
+    }
+  }
+  return n;
+}
+
+std::unique_ptr<Block> ErasureConsensus::recover_from(const Address& a, int want, bool parallel,
+                                                      size_t* rewritten) {
   const int k = o_.k, m = o_.m, total = k + m;
   const std::string what = "erasure: reassembled block does not match its address";
   bool any_down = false;
@@ -1464,20 +1509,8 @@ std::unique_ptr<Block> ErasureConsensus::recover_from(const Address& a, int want
     if (!chb_valid(a, h.salt, h.owner, block)) continue;
     // the block is verified: every shard in hand that differs from its
     // re-encoding is rewritten on the holder that served it
-    Buffer parity((size_t)m * S);
-    codec_.encode(k, m, S, 1, padded_block.data(), parity.data());
-    const ShardKeys keys(a);
-    for (const auto& sh : have) {
-      const int i = sh.first;
-      const uint8_t* want = i < k ? padded_block.data() + (size_t)i * S : parity.data() + (size_t)(i - k) * S;
-      if (std::memcmp(sh.second.data() + ShardHeader::kSize, want, S) == 0 || !from[i]) continue;
-      try {
-        from[i]->store(keys(i), encode_shard(h, want, i));
-        ++corrupt_rewritten_;
-      } catch (Error&) {
-        // unreachable now: the next fetch or repair meets it again
-      }
-    }
+    const size_t nw = rewrite_disagreeing(a, h, padded_block, have, from);
+    if (rewritten) *rewritten += nw;
     ++subset_recoveries_;
     ++fetched_;
     auto b = std::make_unique<Block>();
@@ -2240,6 +2273,150 @@ ErasureConsensus::RepairReport ErasureConsensus::expand() {
         }
   }
   return repair_blocks(under, false);
+}
+
+ErasureConsensus::ScrubReport ErasureConsensus::scrub(const std::vector<Address>* only) {
+  std::lock_guard<std::mutex> rl(repair_mu_);
+  const int k = o_.k, m = o_.m, total = k + m;
+  ScrubReport rep;
+  // the blocks, their shard sizes and recorded holders, under one short
+  // reader lock (the gathers below take it per block, never across a chunk)
+  struct Item {
+    Address a;
+    size_t S;
+    std::vector<Address> holder;
+  };
+  std::vector<Item> items;
+  {
+    std::shared_lock<std::shared_mutex> g(index_mu_);
+    auto add = [&](const Address& a, const Placement& pl) {
+      items.push_back({a, memo_ec_shard_size(pl.B, k), pl.holder});
+    };
+    if (only) {
+      for (const Address& a : *only) {
+        auto it = index_.find(a);
+        if (it != index_.end()) add(a, it->second);
+      }
+    } else {
+      items.reserve(index_.size());
+      for (auto& kv : index_) add(kv.first, kv.second);
+    }
+  }
+  // one block's shards in hand
+  struct Got {
+    ShardHeader h;
+    std::vector<std::pair<int, Buffer>> have;  // sorted by index; all k + m or skipped
+    std::vector<Node*> from;
+    bool complete = false;
+  };
+  size_t i0 = 0;
+  while (i0 < items.size()) {
+    // a chunk of at most stage_bytes of shards (at least one block)
+    size_t i1 = i0, bytes = 0;
+    while (i1 < items.size()) {
+      const size_t b = (size_t)total * items[i1].S;
+      if (i1 > i0 && bytes + b > o_.stage_bytes) break;
+      bytes += b;
+      ++i1;
+    }
+    const size_t cn = i1 - i0;
+    std::vector<Got> got(cn);
+    pool_.parallel_for(cn, [&](size_t t) {
+      Got& g = got[t];
+      g.from.assign(total, nullptr);
+      // An unplaced shard, or a recorded holder that is evicted or known to
+      // be down: skipped before anything is read (a gather would go on to
+      // ask every node of the overlay for the missing shard).
+      const Item& it = items[i0 + t];
+      if ((int)it.holder.size() < total) return;
+      for (int i = 0; i < total; ++i) {
+        const auto nd = it.holder[i] ? overlay_.node(it.holder[i]) : nullptr;
+        if (!nd || nd->evicted || !nd->up) return;
+      }
+      bool any_down = false;
+      try {
+        g.have = gather_shards(it.a, total, any_down, &g.h, false, &g.from);
+      } catch (Error&) {
+        return;  // skipped
+      }
+      std::sort(g.have.begin(), g.have.end(),
+                [](const auto& x, const auto& y) { return x.first < y.first; });
+      g.complete = (int)g.have.size() == total && g.h.shard_size == items[i0 + t].S;
+    });
+    // groups of one shard size: one verify call each
+    std::map<size_t, std::vector<size_t>> groups;
+    for (size_t t = 0; t < cn; ++t) {
+      ++rep.blocks_checked;
+      if (got[t].complete) groups[got[t].h.shard_size].push_back(t);
+      else ++rep.blocks_skipped;
+    }
+    for (auto& kv : groups) {
+      const size_t S = kv.first, n = kv.second.size();
+      auto data = arena_.lease(n * k * S), parity = arena_.lease(n * m * S);
+      auto words = arena_.lease(n * sizeof(uint32_t));
+      uint32_t* verdict = reinterpret_cast<uint32_t*>(words.data());
+      pool_.parallel_for(n, [&](size_t x) {
+        const Got& g = got[kv.second[x]];
+        for (int i = 0; i < total; ++i) {
+          uint8_t* dst = i < k ? data.data() + (x * k + i) * S : parity.data() + (x * m + (i - k)) * S;
+          if (S) std::memcpy(dst, g.have[i].second.data() + ShardHeader::kSize, S);
+        }
+      });
+      codec_.verify(k, m, S, n, data.data(), parity.data(), verdict,
+                    data.pinned() && parity.pinned() && words.pinned());
+      ++rep.codec_calls;
+      for (size_t x = 0; x < n; ++x) {
+        const Verdict v = decode_verdict(verdict[x]);
+        if (v.clean()) {
+          ++rep.blocks_clean;
+          continue;
+        }
+        ++rep.mismatches;
+        const Got& g = got[kv.second[x]];
+        const Address& a = items[i0 + kv.second[x]].a;
+        // The located shard: with its bytes replaced by what the others give,
+        // does the block pass its address?  (The hash is the judge: the code
+        // cannot both locate one wrong shard and detect two.)
+        bool fixed = false;
+        if (v.located() && v.shard < total) {
+          Buffer block(data.data() + x * k * S, data.data() + (x + 1) * k * S);  // k x S
+          if (v.shard < k) {
+            // rebuild data shard j from the k lowest other shards
+            std::vector<uint8_t> sidx;
+            Buffer surv((size_t)k * S), out(S);
+            for (int i = 0; i < total && (int)sidx.size() < k; ++i) {
+              if (i == v.shard) continue;
+              std::memcpy(surv.data() + sidx.size() * S, g.have[i].second.data() + ShardHeader::kSize, S);
+              sidx.push_back((uint8_t)i);
+            }
+            const uint8_t lost = (uint8_t)v.shard;
+            codec_.rebuild(k, m, S, 1, sidx.data(), surv.data(), &lost, 1, out.data());
+            std::memcpy(block.data() + (size_t)v.shard * S, out.data(), S);
+          }
+          // (a parity shard: the data shards stand as they are, and the
+          // re-encoding below is that shard rebuilt)
+          Buffer unpadded(block.begin(), block.begin() + g.h.block_size);
+          if (chb_valid(a, g.h.salt, g.h.owner, unpadded)) {
+            rep.shards_rewritten += rewrite_disagreeing(a, g.h, block, g.have, g.from);
+            fixed = true;
+          }
+        }
+        if (!fixed) {
+          try {
+            recover(a, true, &rep.shards_rewritten);
+          } catch (Error&) {
+            ++rep.unrecoverable;  // nothing was touched
+          }
+        }
+      }
+    }
+    i0 = i1;
+  }
+  scrubbed_blocks_ += rep.blocks_checked;
+  scrub_mismatches_ += rep.mismatches;
+  scrub_rewritten_ += rep.shards_rewritten;
+  scrub_unrecoverable_ += rep.unrecoverable;
+  return rep;
 }
 
 size_t ErasureConsensus::rescan() {

@@ -53,6 +53,11 @@ class Codec {
   // the library DMAs straight from them, no bounce copies)
   void encode(int k, int m, size_t S, size_t n, const uint8_t* data, uint8_t* parity,
               bool pinned = false);
+  // verdict[b] (n words): 0 when block b's k data and m stored parity shards
+  // agree, else mismatching parity rows | located shard << 16
+  // (memo_ec_verify_batch); pinned covers all three buffers.
+  void verify(int k, int m, size_t S, size_t n, const uint8_t* data, const uint8_t* parity,
+              uint32_t* verdict, bool pinned = false);
   void rebuild(int k, int m, size_t S, size_t n, const uint8_t* surv_idx, const uint8_t* surv,
                const uint8_t* lost_idx, int e, uint8_t* out, bool pinned = false);
   // One erasure pattern for all n blocks (memo_ec_rebuild_uniform):
@@ -65,6 +70,7 @@ class Codec {
   // (memo_ec_rebuild_segments); every device takes its share of every group.
   void rebuild_segments(const std::vector<memo_ec_rebuild_segment>& segs, bool pinned = false);
   uint64_t encode_calls() const { return encode_calls_; }
+  uint64_t verify_calls() const { return verify_calls_; }
   uint64_t rebuild_calls() const { return rebuild_calls_; }
   uint64_t uniform_calls() const { return uniform_calls_; }
   uint64_t segments_calls() const { return segments_calls_; }
@@ -88,8 +94,24 @@ class Codec {
   std::vector<Dev> dev_;
   std::atomic<size_t> rr_{0};
   std::atomic<uint64_t> encode_calls_{0}, rebuild_calls_{0}, uniform_calls_{0}, segments_calls_{0},
-      uniform_segments_{0};
+      uniform_segments_{0}, verify_calls_{0};
 };
+
+// A memo_ec_verify_batch verdict word taken apart: the stored parity rows
+// that mismatch, and the single shard that explains them (-1: none does).
+struct Verdict {
+  uint32_t mask = 0;
+  int shard = -1;
+  bool clean() const { return mask == 0; }
+  bool located() const { return shard >= 0; }
+};
+inline Verdict decode_verdict(uint32_t word) {
+  Verdict v;
+  v.mask = MEMO_EC_VERDICT_MASK(word);
+  const uint32_t s = MEMO_EC_VERDICT_SHARD(word);
+  v.shard = (v.mask == 0 || s == MEMO_EC_VERDICT_UNLOCATED) ? -1 : (int)s;
+  return v;
+}
 
 // ------------------------------------------------------- pinned arena
 // Reusable page-locked batch buffers (memo_ec_host_alloc).  The codec's
@@ -354,6 +376,43 @@ class ErasureConsensus : public StackedConsensus {
   // on a new owner.  With include_down, shards on nodes that are merely
   // unreachable count as lost too.  A full scan of the index.
   RepairReport repair(bool include_down = false);
+  struct ScrubReport {
+    // blocks_checked = blocks_clean + blocks_skipped + mismatches
+    size_t blocks_checked = 0, blocks_clean = 0, blocks_skipped = 0;
+    size_t mismatches = 0, shards_rewritten = 0, unrecoverable = 0, codec_calls = 0;
+    ScrubReport& operator+=(const ScrubReport& o) {
+      blocks_checked += o.blocks_checked;
+      blocks_clean += o.blocks_clean;
+      blocks_skipped += o.blocks_skipped;
+      mismatches += o.mismatches;
+      shards_rewritten += o.shards_rewritten;
+      unrecoverable += o.unrecoverable;
+      codec_calls += o.codec_calls;
+      return *this;
+    }
+    // every block accounted for once, no more rewrites than shards, no more
+    // unrecoverable blocks than mismatches
+    bool consistent(int shards_per_block) const {
+      return blocks_checked == blocks_clean + blocks_skipped + mismatches &&
+             unrecoverable <= mismatches &&
+             shards_rewritten <= (mismatches - unrecoverable) * (size_t)shards_per_block;
+    }
+  };
+  // Do the k + m shards of each block still agree with each other?  A
+  // healthy fetch reads only the data shards, so a well-framed parity shard
+  // with wrong bytes goes unnoticed until a degraded fetch needs it.  scrub()
+  // reads every shard of every block (`only`: of the listed blocks that are
+  // placed) in chunks of at most stage_bytes, verifies them on the GPU, one
+  // codec call per shard size (memo_ec_verify_batch), and repairs what
+  // disagrees: a located shard is rebuilt from the others and, once the
+  // reassembled block passes its CHB address, rewritten on its holder; an
+  // unlocated mismatch, or a located one whose block fails the address,
+  // goes to the k-subset recovery of a failed fetch, and is counted
+  // unrecoverable (and left untouched) when that finds no good subset.
+  // Blocks with an unreachable holder or a missing or CRC-invalid shard are
+  // skipped: repair()'s business.  An explicit call like repair(), no timer;
+  // it sends only shard fetches and shard stores.
+  ScrubReport scrub(const std::vector<Address>* only = nullptr);
   // Evict a node now (Paxos::LocalPeer::_disappeared_evict, Paxos.cc:1012-
   // 1087): only the blocks the per-node index lists for it are repaired.
   RepairReport evict(const Address& node);
@@ -473,10 +532,17 @@ class ErasureConsensus : public StackedConsensus {
   // A block whose reassembly failed its address, from another k-subset of
   // its reachable shards; the disagreeing shards rewritten (AddressMismatch
   // when no subset within verify_subsets matches).
-  std::unique_ptr<Block> recover(const Address& a, bool parallel);
+  // (*rewritten, when given, is advanced by the shards rewritten)
+  std::unique_ptr<Block> recover(const Address& a, bool parallel, size_t* rewritten = nullptr);
   // recover() from the first `want` shards gathered: null when none of its
   // subsets matches and a wider gather is left to try
-  std::unique_ptr<Block> recover_from(const Address& a, int want, bool parallel);
+  std::unique_ptr<Block> recover_from(const Address& a, int want, bool parallel,
+                                      size_t* rewritten = nullptr);
+  // The shards in `have` that disagree with the verified k x S block
+  // rewritten on the holders that served them (recover_from and scrub).
+  size_t rewrite_disagreeing(const Address& a, const ShardHeader& h, const Buffer& padded_block,
+                             const std::vector<std::pair<int, Buffer>>& have,
+                             const std::vector<Node*>& from);
   // index_ updates under index_mu_ (held exclusively by the caller); they
   // return the block's previous holders for the node index, which the
   // caller updates after releasing the lock
@@ -527,6 +593,10 @@ class ErasureConsensus : public StackedConsensus {
   // reassemblies that failed their address and were recovered from another
   // k-subset; shards found wrong that way and rewritten
   std::atomic<uint64_t> subset_recoveries_{0}, corrupt_rewritten_{0};
+  // scrub(): blocks verified or skipped, blocks whose shards disagreed,
+  // shards rewritten, blocks no k-subset of whose shards matches the address
+  std::atomic<uint64_t> scrubbed_blocks_{0}, scrub_mismatches_{0}, scrub_rewritten_{0},
+      scrub_unrecoverable_{0};
   const OwnerDirectory* owners_ = nullptr;
   mutable std::mutex rm_mu_;
   // Shard removals owed to a node that was down: the block, the shard index

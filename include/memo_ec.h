@@ -199,6 +199,31 @@ int memo_ec_generator(int k, int m, uint8_t *out);
 int memo_ec_encode_batch(memo_ec_ctx *ctx, int k, int m, size_t S, size_t n,
                          const uint8_t *data, uint8_t *parity, int where);
 
+/* Do the k data and m parity shards of each block still agree, and if not,
+ * which shard is wrong?  Reads every shard once and writes one word per
+ * block:
+ * verdict[b] (n words): 0 = the k data and m parity shards of block b agree.
+ * Otherwise bits 0..15 (MEMO_EC_VERDICT_MASK) have bit i set iff stored
+ * parity shard i differs anywhere from the parity recomputed from the data
+ * shards, and bits 16..23 (MEMO_EC_VERDICT_SHARD) name the single shard that
+ * explains every mismatch: k + i when parity row i alone differs, the data
+ * shard j when all m rows differ and their syndromes s_i (stored XOR
+ * recomputed) satisfy s_i[p] * g_0j == g_ij * s_0[p] at every byte p, with
+ * g_ij = 1 / ((k + i) ^ j); MEMO_EC_VERDICT_UNLOCATED when no single shard
+ * does, and always for m == 1 (one syndrome detects but cannot locate).
+ * Bits 24..31 are zero.  A located shard is the code's best explanation, not
+ * a proof: with m = 2 two wrong shards can pass for one, so callers check
+ * the repaired block against its hash.
+ * A mismatch is a result, not an error.  m == 0 or n == 0 writes nothing.
+ * `where` as for memo_ec_encode_batch, and names the memory of all three
+ * buffers; MEMO_EC_DEVICE: asynchronous on the ctx stream. */
+#define MEMO_EC_VERDICT_MASK(v) ((uint32_t)(v) & 0xFFFFu)
+#define MEMO_EC_VERDICT_SHARD(v) (((uint32_t)(v) >> 16) & 0xFFu)
+#define MEMO_EC_VERDICT_UNLOCATED 0xFFu
+int memo_ec_verify_batch(memo_ec_ctx *ctx, int k, int m, size_t S, size_t n,
+                         const uint8_t *data, const uint8_t *parity,
+                         uint32_t *verdict, int where);
+
 /* Rebuild the e lost shards of each block from its k survivors.  A lost
  * index may name a data or a parity shard.  e == 0 is a no-op. */
 int memo_ec_rebuild_batch(memo_ec_ctx *ctx, int k, int m, size_t S, size_t n,

@@ -41,8 +41,12 @@ constexpr int DEC_IDX_REGS = 2;
 // MAC_IMAGES: a rebuild over per-block table images -- the encode's code
 // under a kernel name of its own (gf_mac_images_kernel), so traces tell a
 // rebuild MAC from an encode.
+// MAC_VERIFY: the encode's multiply-accumulate with the stores replaced by
+// loads of the stored parity and a compare (gf_verify_kernel): `out` is the
+// stored parity, read only, and mismatching rows are ORed into `verdict`.
 enum MacMode : int { MAC_ENCODE = 0, MAC_ROWS = 1, MAC_FUSED = 2, MAC_PROBE = 3, MAC_IMAGES = 4,
-                     MAC_PERM = 5 /* MEMO_EC_PERM_PROBE builds only (tools/perm_probe.py) */ };
+                     MAC_PERM = 5 /* MEMO_EC_PERM_PROBE builds only (tools/perm_probe.py) */,
+                     MAC_VERIFY = 6 };
 
 // LDS bytes of the fused rebuild's decode workspace for a tile of ns blocks:
 // GF log/antilog (1 KiB), LW0 (128 B), per block 3 survivor-mask words + a
@@ -86,6 +90,7 @@ struct MacSeg {
   uint32_t m;             // parity shards of the code (kin + m = shard count)
   uint32_t ws_dw;         // LDS dword offset of the decode workspace
   uint32_t probe;         // stream_probe_kernel: a memo_ec_probe_mode
+  uint32_t* verdict;      // gf_verify_kernel: block b's verdict word at verdict + b
 };
 
 struct MacLaunch {
@@ -132,6 +137,15 @@ struct Sha256Args {
   uint64_t n, prefix_len, prefix_stride, msg_stride, uniform_len;
 };
 
+// verify_locate_kernel: fills the shard field of the nonzero verdict words.
+struct LocateArgs {
+  const uint8_t* data;    // n x k x S
+  const uint8_t* parity;  // n x m x S (the stored parity)
+  uint32_t* verdict;      // n words: mask from gf_verify_kernel in, mask | shard << 16 out
+  uint64_t n, S;
+  uint32_t k, m;
+};
+
 struct FillArgs {
   uint8_t* out;
   uint64_t seed, first_block, n, B, stride;
@@ -158,6 +172,7 @@ hipError_t launch_mac(int KC, int R, int mode, const MacLaunch& L, uint32_t grid
 void lw0_host(int k, int m, uint8_t* out);
 hipError_t launch_decode_coef(const DecodeArgs& a, hipStream_t st);  // closed-form decode rows
 hipError_t launch_decode_multi(const DecodeArgs* a, int n, hipStream_t st);  // several segments
+hipError_t launch_verify_locate(const LocateArgs& a, hipStream_t st);
 hipError_t launch_fill(const FillArgs& a, hipStream_t st);
 hipError_t launch_sha256(const Sha256Args& a, hipStream_t st);
 hipError_t launch_gather(const GatherArgs& a, hipStream_t st);

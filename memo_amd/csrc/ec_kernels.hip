@@ -839,8 +839,15 @@ __device__ __forceinline__ void dec_wave_tile(const MacSeg& sg, const Unit& u, c
 // (MAC_FUSED).
 template <int KC, int R, bool NT, int MODE>
 __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32_t* s_tab) {
-  constexpr bool COEF = MODE != MAC_ENCODE;  // tables built in LDS from coefficients
+  constexpr bool VERIFY = MODE == MAC_VERIFY;  // the encode path, compare in place of stores
+  constexpr bool COEF = MODE != MAC_ENCODE && !VERIFY;  // tables built in LDS from coefficients
   constexpr bool FUSED = MODE == MAC_FUSED;
+  // Verify: the stored parity rows are loaded right behind the shard loads
+  // (4 more registers per row live through the MAC: the k = 16, R = 4 body
+  // goes from 132 to 139 VGPRs and keeps its 3 waves per SIMD); the R > 4
+  // bodies load them after the MAC.
+  constexpr bool PV_EARLY = VERIFY && R <= 4;
+  uint4 pv[VERIFY ? R : 1];
   const uint32_t kin = sg.kin, kpad = sg.kpad;
   const uint32_t set_dw = R * kpad * 8;
 
@@ -969,6 +976,11 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
     uint4 d[KC];
 #pragma unroll
     for (int g = 0; g < KC; ++g) d[g] = ld16<NT>(u.in(sg, g));
+    if constexpr (PV_EARLY) {
+#pragma unroll
+      for (int i = 0; i < R; ++i)
+        if ((uint32_t)i < sg.r) pv[i] = ld16<NT>(u.out(sg, i));
+    }
     if constexpr (COEF) store_images<R, KC>(sg, u, tv, s_tab);
     else store_tables(sg, u, set_dw, tv, s_tab);
     __syncthreads();
@@ -986,7 +998,27 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
     }
   }
 
-  if (u.valid) {
+  if constexpr (VERIFY) {
+    // Stored parity row i (i < r: the padded rows r..R-1 are never compared)
+    // against acc[i].  Lanes past the tile's columns read a real column
+    // (locate clamps them) and report nothing.  Only a mismatching lane
+    // writes: bit i into the verdict word of ITS block (a flat tile spans
+    // several), so clean data stores nothing.
+    if (!(PV_EARLY && kin == KC)) {
+#pragma unroll
+      for (int i = 0; i < R; ++i)
+        if ((uint32_t)i < sg.r) pv[i] = ld16<NT>(u.out(sg, i));
+    }
+    uint32_t bad = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+      if ((uint32_t)i < sg.r) {
+        const uint32_t x = (pv[i].x ^ acc[i][0]) | (pv[i].y ^ acc[i][1]) | (pv[i].z ^ acc[i][2]) |
+                           (pv[i].w ^ acc[i][3]);
+        bad |= x ? 1u << i : 0u;
+      }
+    if (u.valid && bad) atomicOr(sg.verdict + u.b_first + u.set, bad);
+  } else if (u.valid) {
 #pragma unroll
     for (int i = 0; i < R; ++i)
       if ((uint32_t)i < sg.r)
@@ -1025,6 +1057,132 @@ __global__ void __launch_bounds__(256) gf_mac_images_kernel(const MacLaunch L) {
   uint64_t tile;
   if (!seg_tile(L, sid, tile)) return;
   mac_tile<KC, R, NT, MAC_ENCODE>(L.seg[sid], tile, s_tab);
+}
+
+// Parity verify: the encode's tiles, table image, shard loads and MAC; each
+// lane then compares its 16 bytes of every stored parity row with what it
+// computed and ORs the mismatching rows into its block's verdict word
+// (bits 0..15 of memo_ec_verify_batch's verdict).  Reads (k + m) * S bytes
+// per block and writes nothing for a consistent one.
+template <int KC, int R, bool NT>
+__global__ void __launch_bounds__(256) gf_verify_kernel(const MacLaunch L) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];
+  uint32_t sid;
+  uint64_t tile;
+  if (!seg_tile(L, sid, tile)) return;
+  mac_tile<KC, R, NT, MAC_VERIFY>(L.seg[sid], tile, s_tab);
+}
+
+// The shard field (bits 16..23) of the nonzero verdict words: the single
+// shard that explains every mismatch, or 0xFF.  With s_i[p] = stored parity i
+// XOR recomputed parity i at byte p and g_ij = 1 / ((k + i) ^ j):
+//   m == 1                     -> 0xFF (one syndrome detects, cannot locate)
+//   one row i mismatches       -> k + i (a wrong data byte makes every
+//                                 syndrome nonzero there: all g_ij != 0)
+//   all m rows mismatch, m >= 2 -> the data shard j < k with
+//                                 s_i[p] * g_0j == g_ij * s_0[p] for every
+//                                 byte p and row i (unique: g_1j / g_0j is
+//                                 injective in j), else 0xFF
+//   any other mask             -> 0xFF
+// Cold path, written to be read: a fixed grid whose workgroups stride over
+// the verdict array 64 words at a time, one word per lane; each wave ballots
+// the nonzero words and the workgroup takes those blocks one at a time, its
+// 256 lanes striding over the block's dwords, each with a bit set of the data
+// shards still consistent with every byte it saw (AND over all positions:
+// the answer does not depend on their order, nor on which lane saw which).
+// A clean batch costs the read of its 4 * n verdict bytes.  KMAX bounds k:
+// a lane's k data dwords of one position are loaded together, ahead of the
+// arithmetic (one memory latency per position, not k).
+
+// c * x for the 4 bytes of x.
+__device__ __forceinline__ uint32_t gf_mul4(const uint8_t* lg, const uint8_t* ex, uint32_t c,
+                                            uint32_t x) {
+  return gf_mul_t(lg, ex, c, x & 0xFFu) | (gf_mul_t(lg, ex, c, (x >> 8) & 0xFFu) << 8) |
+         (gf_mul_t(lg, ex, c, (x >> 16) & 0xFFu) << 16) | (gf_mul_t(lg, ex, c, x >> 24) << 24);
+}
+
+template <int KMAX>
+__global__ void __launch_bounds__(256) verify_locate_kernel(const LocateArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_gf[kGfDwords];
+  __shared__ uint8_t s_g[MEMO_EC_MAX_M * MEMO_EC_MAX_K];  // g_ij at i * k + j
+  __shared__ uint32_t s_word[64];                         // the workgroup's 64 verdict words
+  __shared__ uint32_t s_cand[2];                          // AND of the lanes' candidate sets
+  const uint8_t* lg = reinterpret_cast<const uint8_t*>(s_gf);
+  const uint8_t* ex = lg + 256;
+  const uint32_t k = a.k, m = a.m;
+  stage_gf(s_gf);
+  __syncthreads();
+  for (uint32_t x = threadIdx.x; x < m * k; x += blockDim.x) {
+    const uint32_t i = x / k, j = x - i * k;
+    s_g[x] = ex[255u - lg[(k + i) ^ j]];  // (k + i) ^ j != 0: j < k <= k + i
+  }
+  const uint32_t tid = threadIdx.x, lane = tid % 64;
+  const uint32_t all = (1u << m) - 1u;  // m <= 16
+  const uint64_t kbits = k >= 64 ? ~0ull : (1ull << k) - 1ull;
+  const uint64_t dwords = a.S / 4;
+  for (uint64_t base = (uint64_t)blockIdx.x * 64; base < a.n; base += (uint64_t)gridDim.x * 64) {
+    __syncthreads();  // s_g staged; the previous round's s_word all read
+    if (tid < 64) s_word[tid] = base + tid < a.n ? a.verdict[base + tid] : 0u;
+    __syncthreads();
+    const uint32_t word = s_word[lane];
+    uint64_t flagged = __ballot(word != 0);
+    while (flagged) {  // uniform over the workgroup: every wave holds the same words
+      const uint32_t src = (uint32_t)__builtin_ctzll(flagged);
+      flagged &= flagged - 1;
+      const uint64_t b = base + src;
+      const uint32_t mask = s_word[src] & 0xFFFFu;
+      uint32_t shard = MEMO_EC_VERDICT_UNLOCATED;
+      if (m >= 2 && __popc(mask) == 1) {
+        shard = k + (uint32_t)__builtin_ctz(mask);
+      } else if (m >= 2 && mask == all) {
+        if (tid < 2) s_cand[tid] = ~0u;
+        __syncthreads();
+        const uint32_t* d = reinterpret_cast<const uint32_t*>(a.data + b * k * a.S);
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(a.parity + b * m * a.S);
+        uint64_t cand = kbits;  // data shards consistent with every byte this lane saw
+        for (uint64_t w = tid; w < dwords && cand; w += 256) {
+          uint32_t dv[KMAX];
+#pragma unroll
+          for (int j = 0; j < KMAX; ++j) dv[j] = (uint32_t)j < k ? d[j * dwords + w] : 0u;
+          uint32_t pn = p[w], s0 = 0;
+          for (uint32_t i = 0; i < m; ++i) {
+            uint32_t si = pn;  // stored parity row i, then its syndrome
+            if (i + 1 < m) pn = p[(i + 1) * dwords + w];
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j)
+              if ((uint32_t)j < k) si ^= gf_mul4(lg, ex, s_g[i * k + j], dv[j]);
+            if (i == 0) {
+              s0 = si;
+              continue;
+            }
+            // Consistent bytes (both syndromes 0) keep every candidate; a byte
+            // with s_0 == 0 and s_i != 0 drops them all (every g is nonzero).
+            if ((s0 | si) == 0) continue;
+            for (uint64_t c = cand; c; c &= c - 1) {
+              const uint32_t j = (uint32_t)__builtin_ctzll(c);
+              if (gf_mul4(lg, ex, s_g[j], si) != gf_mul4(lg, ex, s_g[i * k + j], s0))
+                cand &= ~(1ull << j);
+            }
+          }
+        }
+        // AND over the wave's lanes, then over the workgroup's waves
+        uint32_t lo = (uint32_t)cand, hi = (uint32_t)(cand >> 32);
+        for (int off = 32; off; off >>= 1) {
+          lo &= (uint32_t)__shfl_xor((int)lo, off);
+          hi &= (uint32_t)__shfl_xor((int)hi, off);
+        }
+        if (lane == 0) {
+          atomicAnd(&s_cand[0], lo);
+          atomicAnd(&s_cand[1], hi);
+        }
+        __syncthreads();
+        cand = ((uint64_t)s_cand[1] << 32) | s_cand[0];
+        __syncthreads();  // read before the next block resets it
+        if (__popcll(cand) == 1) shard = (uint32_t)__builtin_ctzll(cand);
+      }
+      if (tid == 0) a.verdict[b] = mask | (shard << 16);
+    }
+  }
 }
 
 #ifdef MEMO_EC_PERM_PROBE
@@ -1907,6 +2065,8 @@ static hipError_t launch_mac_t(int mode, const MacLaunch& L, uint32_t grid, size
     hipLaunchKernelGGL((gf_mac_kernel<KC, R, MAC_NT, true>), dim3(grid), dim3(256), lds, st, L);
   else if (mode == MAC_IMAGES)
     hipLaunchKernelGGL((gf_mac_images_kernel<KC, R, MAC_NT>), dim3(grid), dim3(256), lds, st, L);
+  else if (mode == MAC_VERIFY)
+    hipLaunchKernelGGL((gf_verify_kernel<KC, R, MAC_NT>), dim3(grid), dim3(256), lds, st, L);
 #ifdef MEMO_EC_PERM_PROBE
   else if (mode == MAC_PERM)
     hipLaunchKernelGGL((gf_mac_perm_kernel<KC, R, MAC_NT>), dim3(grid), dim3(256), lds, st, L);
@@ -2099,6 +2259,18 @@ hipError_t launch_decode_multi(const DecodeArgs* as, int na, hipStream_t st) {
 }
 
 hipError_t launch_decode_coef(const DecodeArgs& a, hipStream_t st) { return launch_decode_multi(&a, 1, st); }
+
+hipError_t launch_verify_locate(const LocateArgs& a, hipStream_t st) {
+  if (a.n == 0) return hipSuccess;
+  // fixed grid: one workgroup per 64 verdict words, at most 2048 (8 per CU)
+  uint64_t grid = (a.n + 63) / 64;
+  if (grid > 2048) grid = 2048;
+  if (a.k <= 16)
+    hipLaunchKernelGGL(verify_locate_kernel<16>, dim3((uint32_t)grid), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(verify_locate_kernel<MEMO_EC_MAX_K>, dim3((uint32_t)grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
 
 hipError_t launch_fill(const FillArgs& a, hipStream_t st) {
   const uint64_t total = a.n * (a.stride / 16);

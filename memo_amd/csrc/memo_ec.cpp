@@ -636,6 +636,38 @@ int encode_device(memo_ec_ctx* ctx, int k, int m, size_t S, size_t n, const uint
   return MEMO_EC_OK;
 }
 
+// Device-resident verify on stream st: the verdict words zeroed, the verify
+// launches (the encode's geometry, split like encode_device's), then the
+// locate pass over the words they flagged.
+int verify_device(memo_ec_ctx* ctx, int k, int m, size_t S, size_t n, const uint8_t* data,
+                  const uint8_t* parity, uint32_t* verdict, hipStream_t st) {
+  const int R = mac_rbound(m), KC = mac_kchunk(k, R);
+  const uint32_t* tab = nullptr;
+  if (int rc = encode_tables(ctx, k, m, R, KC, &tab)) return rc;
+  HIPCHK(hipMemsetAsync(verdict, 0, n * sizeof(uint32_t), st));
+  const size_t step = max_blocks_per_launch(ctx, S);
+  for (size_t b0 = 0; b0 < n; b0 += step) {
+    const size_t cnt = std::min(step, n - b0);
+    // `out` is the stored parity: MAC_VERIFY only reads it
+    Plan p = plan_segment((uint32_t)k, (uint32_t)m, S, cnt, data + b0 * (size_t)k * S,
+                          (uint64_t)k * S, S, const_cast<uint8_t*>(parity) + b0 * (size_t)m * S,
+                          (uint64_t)m * S, S, tab, 0, KC, R);
+    p.mode = MAC_VERIFY;
+    p.seg.verdict = verdict + b0;
+    std::vector<Plan> plans{p};
+    if (int rc = launch_plans(ctx, plans, st)) return rc;
+  }
+  LocateArgs a{};
+  a.data = data;
+  a.parity = parity;
+  a.verdict = verdict;
+  a.n = n;
+  a.S = S;
+  a.k = (uint32_t)k;
+  a.m = (uint32_t)m;
+  return hip_rc(launch_verify_locate(a, st));
+}
+
 DecodeArgs decode_args(const memo_ec_ctx* c, int k, int m, int e, size_t n, const uint8_t* surv_idx,
                        const uint8_t* lost_idx, uint8_t* rows, uint32_t* status, const uint32_t* lw0) {
   DecodeArgs a{};
@@ -868,6 +900,46 @@ int host_mac(memo_ec_ctx* c, size_t n, size_t in_b, size_t out_b, const uint8_t*
       },
       [&](int s, size_t b0, size_t cnt) {
         if (!pinned) par_memcpy(c, out + b0 * out_b, c->h_slot[s] + nb * in_b, cnt * out_b);
+      });
+}
+
+// Host-memory verify through the copy pipeline: each wave's data and parity
+// go to one device slot [data nb*k*S | parity nb*m*S | verdict nb words], the
+// verify and locate run there, and the wave's verdict words come back to
+// their offset in the caller's array.
+int verify_host(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const uint8_t* data,
+                const uint8_t* parity, uint32_t* verdict, bool pinned) {
+  const size_t d_b = (size_t)k * S, p_b = (size_t)m * S, v_b = sizeof(uint32_t);
+  size_t nb = std::max<size_t>(1, c->opt.pipe_bytes / (d_b + p_b));
+  nb = std::min(nb, n);
+  const size_t slot = nb * (d_b + p_b + v_b);
+  if (int rc = ensure_slots(c, slot, pinned ? 0 : slot)) return rc;
+  const size_t p_off = nb * d_b, v_off = nb * (d_b + p_b);
+  return run_pipeline(
+      c, n, nb,
+      [&](int s, size_t b0, size_t cnt, hipStream_t st) -> int {
+        const uint8_t* ds = data + b0 * d_b;
+        const uint8_t* ps = parity + b0 * p_b;
+        if (!pinned) {
+          par_memcpy(c, c->h_slot[s], ds, cnt * d_b);
+          par_memcpy(c, c->h_slot[s] + p_off, ps, cnt * p_b);
+          ds = c->h_slot[s];
+          ps = c->h_slot[s] + p_off;
+        }
+        if (int rc = hip_rc(hipMemcpyAsync(c->d_slot[s], ds, cnt * d_b, hipMemcpyHostToDevice, st)))
+          return rc;
+        return hip_rc(hipMemcpyAsync(c->d_slot[s] + p_off, ps, cnt * p_b, hipMemcpyHostToDevice, st));
+      },
+      [&](int s, size_t, size_t cnt, hipStream_t st) -> int {
+        return verify_device(c, k, m, S, cnt, c->d_slot[s], c->d_slot[s] + p_off,
+                             reinterpret_cast<uint32_t*>(c->d_slot[s] + v_off), st);
+      },
+      [&](int s, size_t b0, size_t cnt, hipStream_t st) -> int {
+        void* dst = pinned ? static_cast<void*>(verdict + b0) : c->h_slot[s] + v_off;
+        return hip_rc(hipMemcpyAsync(dst, c->d_slot[s] + v_off, cnt * v_b, hipMemcpyDeviceToHost, st));
+      },
+      [&](int s, size_t b0, size_t cnt) {
+        if (!pinned) std::memcpy(verdict + b0, c->h_slot[s] + v_off, cnt * v_b);
       });
 }
 
@@ -1424,6 +1496,19 @@ int memo_ec_encode_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const
                   [&](const uint8_t* src, uint8_t* dst, size_t cnt, hipStream_t st) {
                     return encode_device(c, k, m, S, cnt, src, dst, st);
                   });
+}
+
+int memo_ec_verify_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const uint8_t* data,
+                         const uint8_t* parity, uint32_t* verdict, int where) {
+  if (!c) return MEMO_EC_EINVAL;
+  if (int rc = check_km(k, m)) return rc;
+  if (m == 0 || n == 0) return MEMO_EC_OK;
+  if (S == 0 || S % 64 != 0 || !data || !parity || !verdict) return MEMO_EC_EINVAL;
+  if (S >= kMaxShard || too_big(n, (size_t)(k + m) * S)) return MEMO_EC_ERANGE;
+  DeviceGuard g(c->device);
+  if (where == MEMO_EC_DEVICE) return verify_device(c, k, m, S, n, data, parity, verdict, c->stream);
+  if (where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
+  return verify_host(c, k, m, S, n, data, parity, verdict, where == MEMO_EC_HOST_PINNED);
 }
 
 int memo_ec_stream_probe(memo_ec_ctx* c, int kin, int r, size_t S, size_t n, const uint8_t* in,

@@ -78,8 +78,26 @@ EXPORTS = [
     "memo_ec_strerror",
     "memo_ec_version", "memo_ec_device_count", "memo_ec_rebuild_segments",
     "memo_ec_ctx_set_option", "memo_ec_ctx_get_option", "memo_ec_build_id",
-    "memo_ec_device_identity", "memo_ec_stream_probe",
+    "memo_ec_device_identity", "memo_ec_stream_probe", "memo_ec_verify_batch",
 ]
+
+# memo_ec_verify_batch verdict words: MEMO_EC_VERDICT_UNLOCATED of the header.
+VERDICT_UNLOCATED = 0xFF
+
+
+def split_verdict(v):
+    """(mask, shard) of verdict word(s) v (MEMO_EC_VERDICT_MASK / _SHARD):
+    mask bit i = stored parity shard i differs from the recomputed one;
+    shard = the single shard that explains the mismatch, or VERDICT_UNLOCATED.
+    Takes an int, a numpy array or a torch tensor (int32 words read as
+    unsigned)."""
+    if _is_torch(v):
+        v = v.detach().cpu().numpy()
+    if isinstance(v, np.ndarray):
+        u = v.astype(np.int64) & 0xFFFFFFFF
+        return (u & 0xFFFF).astype(np.uint32), ((u >> 16) & 0xFF).astype(np.uint32)
+    u = int(v) & 0xFFFFFFFF
+    return u & 0xFFFF, (u >> 16) & 0xFF
 
 
 def _lib():
@@ -125,6 +143,8 @@ def _lib():
         L.memo_ec_build_id.restype = ctypes.c_char_p
         L.memo_ec_device_identity.argtypes = [c_int, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz]
         L.memo_ec_stream_probe.argtypes = [ctypes.c_void_p, c_int, c_int, _sz, _sz, _u8p, _u8p, c_int]
+        L.memo_ec_verify_batch.argtypes = [ctypes.c_void_p, c_int, c_int, _sz, _sz, _u8p, _u8p,
+                                           ctypes.c_void_p, c_int]
         _LIB = L
     return _LIB
 
@@ -212,6 +232,29 @@ def _ptr(x):
     if isinstance(x, np.ndarray):
         if x.dtype != np.uint8 or not x.flags["C_CONTIGUOUS"]:
             raise TypeError("expected a C-contiguous uint8 array")
+        return x.ctypes.data, HOST
+    raise TypeError("unsupported buffer type %r" % type(x))
+
+
+def _ptr_words(x, n):
+    """(pointer, where) of a buffer of at least n 32-bit words: a torch int32
+    tensor or a numpy uint32 array."""
+    if _is_torch(x):
+        import torch
+        if x.dtype != torch.int32:
+            raise TypeError("expected an int32 tensor")
+        if not x.is_contiguous():
+            raise ValueError("expected a contiguous tensor")
+        if x.numel() < n:
+            raise ValueError("verdict holds %d words, need %d" % (x.numel(), n))
+        if x.is_cuda:
+            return x.data_ptr(), DEVICE
+        return x.data_ptr(), HOST_PINNED if x.is_pinned() else HOST
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.uint32 or not x.flags["C_CONTIGUOUS"]:
+            raise TypeError("expected a C-contiguous uint32 array")
+        if x.size < n:
+            raise ValueError("verdict holds %d words, need %d" % (x.size, n))
         return x.ctypes.data, HOST
     raise TypeError("unsupported buffer type %r" % type(x))
 
@@ -333,6 +376,38 @@ class Codec:
         where = DEVICE if dw == DEVICE else (HOST_PINNED if dw == pw == HOST_PINNED else HOST)
         _check(_lib().memo_ec_encode_batch(self._ctx, k, m, S, n, dp, pp, where), "encode")
         return parity
+
+    def verify(self, k, m, data, parity, verdict=None, S=None, n=None):
+        """verdict (n words) <- do data (n x k x S) and the stored parity
+        (n x m x S) agree: 0, or mask | shard << 16 (split_verdict).  verdict:
+        a numpy uint32 array or torch int32 tensor of n words in the memory
+        the shards live in (made when None); device (async) or host (sync)."""
+        dp, dw = _ptr(data)
+        pp, pw = _ptr(parity)
+        if (dw == DEVICE) != (pw == DEVICE):
+            raise ValueError("data and parity must both be device or both host buffers")
+        if S is None:
+            n, S = _infer_nS(data, k)
+        if verdict is None:
+            # Left unwritten here: the library zeroes the words on the ctx
+            # stream itself, and a fill enqueued on torch's current stream
+            # would not be ordered against that stream's verify (it could
+            # land after it and wipe the verdicts).  m == 0 or n == 0: the
+            # library writes nothing, and nothing races a fill.
+            written = m > 0 and n > 0
+            if _is_torch(data):
+                import torch
+                make = torch.empty if written else torch.zeros
+                verdict = make(n, dtype=torch.int32, device=data.device,
+                               pin_memory=(dw == pw == HOST_PINNED))
+            else:
+                verdict = (np.empty if written else np.zeros)(n, dtype=np.uint32)
+        vp, vw = _ptr_words(verdict, n)
+        if (vw == DEVICE) != (dw == DEVICE):
+            raise ValueError("verdict must live where the shards do (device or host)")
+        where = DEVICE if dw == DEVICE else (HOST_PINNED if dw == pw == vw == HOST_PINNED else HOST)
+        _check(_lib().memo_ec_verify_batch(self._ctx, k, m, S, n, dp, pp, vp, where), "verify")
+        return verdict
 
     def rebuild(self, k, m, surv_idx, surv, lost_idx, out, S=None, n=None):
         """out (n x e x S) <- the k survivor shards surv (n x k x S) of each block."""
