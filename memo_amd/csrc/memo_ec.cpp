@@ -618,22 +618,28 @@ size_t max_blocks_per_launch(const memo_ec_ctx* c, size_t S) {
   return (size_t)std::max<uint64_t>(1, limit / per);
 }
 
+// fn(b0, cnt) over n blocks of S-byte shards, in spans one MAC launch takes.
+template <class Fn>
+int launch_spans(const memo_ec_ctx* c, size_t S, size_t n, Fn fn) {
+  const size_t step = max_blocks_per_launch(c, S);
+  for (size_t b0 = 0; b0 < n; b0 += step)
+    if (int rc = fn(b0, std::min(step, n - b0))) return rc;
+  return MEMO_EC_OK;
+}
+
 // Device-resident encode on stream st.
 int encode_device(memo_ec_ctx* ctx, int k, int m, size_t S, size_t n, const uint8_t* data,
                   uint8_t* parity, hipStream_t st) {
   const int R = mac_rbound(m), KC = mac_kchunk(k, R);
   const uint32_t* tab = nullptr;
   if (int rc = encode_tables(ctx, k, m, R, KC, &tab)) return rc;
-  const size_t step = max_blocks_per_launch(ctx, S);
-  for (size_t b0 = 0; b0 < n; b0 += step) {
-    const size_t cnt = std::min(step, n - b0);
+  return launch_spans(ctx, S, n, [&](size_t b0, size_t cnt) {
     std::vector<Plan> plans{plan_segment((uint32_t)k, (uint32_t)m, S, cnt,
                                          data + b0 * (size_t)k * S, (uint64_t)k * S, S,
                                          parity + b0 * (size_t)m * S, (uint64_t)m * S, S, tab, 0,
                                          KC, R)};
-    if (int rc = launch_plans(ctx, plans, st)) return rc;
-  }
-  return MEMO_EC_OK;
+    return launch_plans(ctx, plans, st);
+  });
 }
 
 // Device-resident verify on stream st: the verdict words zeroed, the verify
@@ -645,9 +651,7 @@ int verify_device(memo_ec_ctx* ctx, int k, int m, size_t S, size_t n, const uint
   const uint32_t* tab = nullptr;
   if (int rc = encode_tables(ctx, k, m, R, KC, &tab)) return rc;
   HIPCHK(hipMemsetAsync(verdict, 0, n * sizeof(uint32_t), st));
-  const size_t step = max_blocks_per_launch(ctx, S);
-  for (size_t b0 = 0; b0 < n; b0 += step) {
-    const size_t cnt = std::min(step, n - b0);
+  const int rc = launch_spans(ctx, S, n, [&](size_t b0, size_t cnt) {
     // `out` is the stored parity: MAC_VERIFY only reads it
     Plan p = plan_segment((uint32_t)k, (uint32_t)m, S, cnt, data + b0 * (size_t)k * S,
                           (uint64_t)k * S, S, const_cast<uint8_t*>(parity) + b0 * (size_t)m * S,
@@ -655,8 +659,9 @@ int verify_device(memo_ec_ctx* ctx, int k, int m, size_t S, size_t n, const uint
     p.mode = MAC_VERIFY;
     p.seg.verdict = verdict + b0;
     std::vector<Plan> plans{p};
-    if (int rc = launch_plans(ctx, plans, st)) return rc;
-  }
+    return launch_plans(ctx, plans, st);
+  });
+  if (rc) return rc;
   LocateArgs a{};
   a.data = data;
   a.parity = parity;
@@ -716,69 +721,6 @@ void with_images(DecodeArgs& a, uint32_t* img, int R, int KC) {
 }
 size_t image_bytes(size_t n, int k, int R, int KC) {
   return n * (size_t)R * kpad_of((uint32_t)k, KC) * 32;
-}
-
-// Device-resident rebuild on stream st.  Fused (default): one launch of
-// gf_rebuild_kernel, whose tiles derive their blocks' decode rows from the
-// indices.  Two-kernel: closed-form decode rows (one lane per block) into
-// `scratch` (room for rebuild_scratch(...)), then the MAC, which builds each
-// block's product tables in LDS from its rows, or (rows_images) reads the
-// table images the decode formed beside the rows.  Faults go to `status`.
-int rebuild_device(memo_ec_ctx* ctx, int k, int m, size_t S, size_t n, const uint8_t* surv_idx,
-                   const uint8_t* surv, const uint8_t* lost_idx, int e, uint8_t* out,
-                   bool fused, void* scratch, hipStream_t st, uint32_t* status) {
-  const int R = mac_rbound(e), KC = mac_kchunk(k, R);
-  const size_t step = max_blocks_per_launch(ctx, S);
-  if (fused) {
-    const uint32_t* lw0 = nullptr;
-    if (int rc = lw0_table(ctx, k, m, &lw0)) return rc;
-    for (size_t b0 = 0; b0 < n; b0 += step) {
-      const size_t cnt = std::min(step, n - b0);
-      Plan p = plan_segment((uint32_t)k, (uint32_t)e, S, cnt, surv + b0 * (size_t)k * S,
-                            (uint64_t)k * S, S, out + b0 * (size_t)e * S, (uint64_t)e * S, S,
-                            nullptr, 0, KC, R, nullptr, (uint64_t)e * k, (uint32_t)e, true);
-      p.seg.sidx = surv_idx + b0 * (size_t)k;
-      p.seg.lidx = lost_idx + b0 * (size_t)e;
-      p.seg.lw0 = lw0;
-      p.seg.status = status;
-      p.seg.m = (uint32_t)m;
-      std::vector<Plan> plans{p};
-      if (int rc = launch_plans(ctx, plans, st)) return rc;
-    }
-    return MEMO_EC_OK;
-  }
-  uint8_t* rows = static_cast<uint8_t*>(scratch);
-  const uint64_t row_b = (uint64_t)e * k;
-  const uint32_t* lw0 = nullptr;
-  if (int rc = lw0_table(ctx, k, m, &lw0)) return rc;
-  DecodeArgs a = decode_args(ctx, k, m, e, n, surv_idx, lost_idx, rows, status, lw0);
-  const bool images = rows_images(ctx, S, k, R, KC);
-  uint32_t* img = reinterpret_cast<uint32_t*>(rows + round256(n * row_b));
-  const uint64_t img_dw = (uint64_t)R * kpad_of((uint32_t)k, KC) * 8;  // per block
-  if (images) with_images(a, img, R, KC);
-  HIPCHK(launch_decode_coef(a, st));
-  for (size_t b0 = 0; b0 < n; b0 += step) {
-    const size_t cnt = std::min(step, n - b0);
-    std::vector<Plan> plans{
-        images ? plan_segment((uint32_t)k, (uint32_t)e, S, cnt, surv + b0 * (size_t)k * S,
-                              (uint64_t)k * S, S, out + b0 * (size_t)e * S, (uint64_t)e * S, S,
-                              img + b0 * img_dw, img_dw, KC, R)
-               : plan_segment((uint32_t)k, (uint32_t)e, S, cnt, surv + b0 * (size_t)k * S,
-                              (uint64_t)k * S, S, out + b0 * (size_t)e * S, (uint64_t)e * S, S,
-                              nullptr, 0, KC, R, rows + b0 * row_b, row_b, (uint32_t)e)};
-    if (images) plans[0].mode = MAC_IMAGES;  // the encode's code under a rebuild name
-    if (int rc = launch_plans(ctx, plans, st)) return rc;
-  }
-  return MEMO_EC_OK;
-}
-
-// Rebuild scratch for n blocks (a multiple of 256 bytes): their decode rows,
-// e x k bytes each, and behind them (rows_images) their table images (the
-// two-kernel path; the fused one needs none).
-size_t rebuild_scratch(const memo_ec_ctx* c, int k, int e, size_t S, size_t n, bool fused) {
-  if (fused) return 0;
-  const int R = mac_rbound(e), KC = mac_kchunk(k, R);
-  return round256(n * (size_t)e * k) + (rows_images(c, S, k, R, KC) ? image_bytes(n, k, R, KC) : 0);
 }
 
 // Deferred-error words in ctx->d_status: device-resident calls (reported by
@@ -853,7 +795,7 @@ int run_pipeline(memo_ec_ctx* c, size_t n, size_t nb, In in, Run run, Out out, D
 }
 
 // A host-memory call of one multiply-accumulate over n blocks of in_b bytes
-// in and out_b bytes out (encode, uniform rebuild): `run(src, dst, cnt, st)`
+// in and out_b bytes out (the encode): `run(src, dst, cnt, st)`
 // enqueues the kernels for cnt blocks of device- or pinned-memory src/dst.
 // Small calls run zero-copy on pinned memory; larger ones through the
 // 3-stage copy pipeline.
@@ -1034,13 +976,18 @@ int pattern_tables(memo_ec_ctx* ctx, int k, int m, const uint8_t* sidx, const ui
   return MEMO_EC_OK;
 }
 
-// ---- Mixed-geometry rebuild (memo_ec_rebuild_segments).
+// ---- Rebuild: every entry point (memo_ec_rebuild_batch, _uniform and
+// _segments) is a list of segments to rebuild_segments_impl.
 // A piece: blocks [b0, b0 + n) of one segment, with the pointers the
 // kernels read (device memory, or pinned host memory for a zero-copy call)
 // and its launch class, fixed once per call: shard chunk KC, row bound R
 // (the class's largest), mode (MAC_ENCODE for a shared pattern, whose
-// product tables `tab` were formed on the host; MAC_FUSED or MAC_ROWS for
-// per-block patterns).
+// product tables `tab` were formed on the host; for per-block patterns
+// MAC_FUSED, one gf_rebuild_kernel launch whose tiles derive their blocks'
+// decode rows from the indices, or MAC_ROWS, closed-form decode rows into
+// the ctx's scratch and then the MAC, which builds each block's product
+// tables in LDS from its rows or (img) reads the table images the decode
+// formed beside them).
 struct RPiece {
   int seg = 0;
   int k = 0, m = 0, e = 0;
@@ -1102,7 +1049,7 @@ int plan_rebuild_segments(memo_ec_ctx* c, int nseg, const memo_ec_rebuild_segmen
   // classes (kind, KC): R = the class's largest bound.  KC = 6, 12, 14 are
   // only chosen for R <= 4, so their classes stay within the instantiated
   // bodies.  Per-block classes take the fused kernel up to the ctx's fused
-  // bound of survivor bytes (as memo_ec_rebuild_batch does per call).
+  // bound of survivor bytes (rebuild_fused).
   struct Cls {
     bool uniform;
     int KC, R;
@@ -1253,12 +1200,10 @@ int launch_rebuild_pieces(memo_ec_ctx* c, const std::vector<RPiece>& ps, uint8_t
     std::vector<Plan> plans;
     for (size_t j : cls[x].pieces) {
       const auto& p = ps[j];
-      const size_t step = max_blocks_per_launch(c, p.S);
       const uint32_t* lw0 = nullptr;
       if (mode == MAC_FUSED)
         if (int rc = lw0_table(c, p.k, p.m, &lw0)) return rc;
-      for (size_t b0 = 0; b0 < p.n; b0 += step) {
-        const size_t cnt = std::min(step, p.n - b0);
+      (void)launch_spans(c, p.S, p.n, [&](size_t b0, size_t cnt) {  // planning only: cannot fail
         const uint64_t in_bs = (uint64_t)p.k * p.S, out_bs = (uint64_t)p.e * p.S;
         const uint8_t* in = p.surv + b0 * in_bs;
         uint8_t* out = p.out + b0 * out_bs;
@@ -1282,7 +1227,8 @@ int launch_rebuild_pieces(memo_ec_ctx* c, const std::vector<RPiece>& ps, uint8_t
           q.seg.m = (uint32_t)p.m;
           plans.push_back(q);
         }
-      }
+        return MEMO_EC_OK;
+      });
     }
     if (waits[x] >= 0) {
       HIPCHK(hipStreamWaitEvent(st, c->side_ev[waits[x]], 0));
@@ -1293,6 +1239,15 @@ int launch_rebuild_pieces(memo_ec_ctx* c, const std::vector<RPiece>& ps, uint8_t
   return MEMO_EC_OK;
 }
 
+// What a call reports once its work is done: the ctx's deferred error, else
+// ESINGULAR when its status word `st` has the singular bit.
+int deferred_rc(memo_ec_ctx* ctx, uint32_t st) {
+  int rc = ctx->deferred;
+  ctx->deferred = 0;
+  if (rc == MEMO_EC_OK && (st & 1u)) rc = MEMO_EC_ESINGULAR;
+  return rc;
+}
+
 int take_deferred(memo_ec_ctx* ctx) {
   uint32_t st = 0;
   HIPCHK(hipMemcpy(&st, ctx->d_status, sizeof st, hipMemcpyDeviceToHost));
@@ -1300,10 +1255,212 @@ int take_deferred(memo_ec_ctx* ctx) {
     const uint32_t z = 0;
     HIPCHK(hipMemcpy(ctx->d_status, &z, sizeof z, hipMemcpyHostToDevice));
   }
-  int rc = ctx->deferred;
-  ctx->deferred = 0;
-  if (rc == MEMO_EC_OK && (st & 1u)) rc = MEMO_EC_ESINGULAR;
-  return rc;
+  return deferred_rc(ctx, st);
+}
+
+// The rebuild of nseg segments in `where` memory, behind every rebuild entry
+// point (which has checked ctx, nseg and segs).
+int rebuild_segments_impl(memo_ec_ctx* c, int nseg, const memo_ec_rebuild_segment* segs, int where) {
+  DeviceGuard g(c->device);
+  std::vector<RPiece> ps;
+  if (int rc = plan_rebuild_segments(c, nseg, segs, ps)) return rc;
+  if (ps.empty()) return MEMO_EC_OK;
+  // Per-block pieces use the ctx's scratch (decode rows, table images) and
+  // its ordering event; a call of shared patterns alone touches neither.
+  bool per_block = false;
+  for (const RPiece& p : ps) per_block |= p.mode != MAC_ENCODE;
+  if (where == MEMO_EC_DEVICE) {
+    if (int rc = ensure_tabs(c, rows_scratch(ps))) return rc;
+    if (int rc = launch_rebuild_pieces(c, ps, reinterpret_cast<uint8_t*>(c->d_tabs), c->stream,
+                                       c->d_status + kStatusDevice))
+      return rc;
+    // marks the scratch busy until these rebuilds are done (host calls check it)
+    return per_block ? hip_rc(hipEventRecord(c->ev_order, c->stream)) : MEMO_EC_OK;
+  }
+  if (where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
+  const bool pinned = where == MEMO_EC_HOST_PINNED;
+  if (per_block) {
+    // device rebuilds still pending on the ctx stream read the same scratch
+    const hipError_t q = hipEventQuery(c->ev_order);
+    if (q == hipErrorNotReady) {
+      HIPCHK(hipStreamWaitEvent(c->sk, c->ev_order, 0));
+    } else if (q != hipSuccess) {
+      return hip_rc(q);
+    }
+  }
+  // Chunks of at most one pipeline batch of survivors, packed in order into
+  // waves of at most one batch; a wave's slot holds [survivors | outputs |
+  // per-block indices].
+  struct Chunk {
+    RPiece p;  // host pointers
+    size_t in, out, idx;
+    size_t o_in = 0, o_out = 0, o_idx = 0;
+  };
+  std::vector<Chunk> ch;
+  const size_t pipe = c->opt.pipe_bytes;
+  size_t total = 0;
+  for (const RPiece& p : ps) {
+    const size_t in_b = (size_t)p.k * p.S, out_b = (size_t)p.e * p.S;
+    const bool uni = p.mode == MAC_ENCODE;
+    const size_t per = std::max<size_t>(1, pipe / in_b);
+    for (size_t b0 = 0; b0 < p.n; b0 += per) {
+      Chunk x;
+      x.p = p;
+      x.p.b0 = b0;
+      x.p.n = std::min(per, p.n - b0);
+      x.p.surv = p.surv + b0 * in_b;
+      x.p.out = p.out + b0 * out_b;
+      if (!uni) {
+        x.p.sidx = p.sidx + b0 * (size_t)p.k;
+        x.p.lidx = p.lidx + b0 * (size_t)p.e;
+      }
+      x.in = x.p.n * in_b;
+      x.out = x.p.n * out_b;
+      x.idx = uni ? 0 : x.p.n * (size_t)(p.k + p.e);
+      total += x.in + x.out + x.idx;
+      ch.push_back(x);
+    }
+  }
+  struct Wave {
+    std::vector<size_t> ids;
+    size_t in = 0, out = 0, idx = 0;
+  };
+  std::vector<Wave> waves;
+  // zero-copy (one wave, whatever its size): the call's survivors, outputs
+  // and per-block indices plus the status word's 64 bytes within the bound
+  const bool zc = total + 64 <= zc_max_bytes(c);
+  for (size_t i = 0; i < ch.size(); ++i) {
+    if (waves.empty() || (!zc && waves.back().in + ch[i].in > pipe)) waves.emplace_back();
+    Wave& w = waves.back();
+    w.ids.push_back(i);
+    w.in += ch[i].in;
+    w.out += ch[i].out;
+    w.idx += ch[i].idx;
+  }
+  // pinned: the survivors and outputs stay in (zero-copy) or move by DMA
+  // from (pipeline) the caller's buffers, so the host slot holds a wave's
+  // indices only (and behind them the zero-copy status word) -- no pinned
+  // bounce buffers of the payload's size
+  auto h_idx = [&](const Wave& w, uint8_t* h) { return h + (pinned ? 0 : w.in + w.out); };
+  size_t slot = 0, hslot = 0, rows = 0;
+  for (Wave& w : waves) {
+    size_t oi = 0, oo = w.in, ox = 0;
+    for (size_t i : w.ids) {
+      ch[i].o_in = oi;
+      ch[i].o_out = oo;
+      ch[i].o_idx = ox;  // within the wave's indices
+      oi += ch[i].in;
+      oo += ch[i].out;
+      ox += ch[i].idx;
+    }
+    slot = std::max(slot, w.in + w.out + w.idx);
+    hslot = std::max(hslot, pinned ? w.idx : w.in + w.out + w.idx);
+    std::vector<RPiece> wp;
+    for (size_t i : w.ids) wp.push_back(ch[i].p);
+    rows = std::max(rows, rows_scratch(wp));  // decode rows + table images (256-byte multiple)
+  }
+  // the pieces as the kernels see them: the wave's indices at idx, survivors
+  // and outputs in slot memory at base or (pinned_io) in the caller's buffers
+  auto staged = [&](const Wave& w, uint8_t* base, const uint8_t* idx, bool pinned_io) {
+    std::vector<RPiece> dp;
+    for (size_t i : w.ids) {
+      RPiece p = ch[i].p;
+      if (!pinned_io) {
+        p.surv = base + ch[i].o_in;
+        p.out = base + ch[i].o_out;
+      }
+      if (p.mode != MAC_ENCODE) {
+        p.sidx = idx + ch[i].o_idx;
+        p.lidx = p.sidx + p.n * (size_t)p.k;
+      }
+      dp.push_back(p);
+    }
+    return dp;
+  };
+  auto stage_idx = [&](const Wave& w, uint8_t* idx) {
+    for (size_t i : w.ids) {
+      const RPiece& p = ch[i].p;
+      if (p.mode == MAC_ENCODE) continue;
+      std::memcpy(idx + ch[i].o_idx, p.sidx, p.n * (size_t)p.k);
+      std::memcpy(idx + ch[i].o_idx + p.n * (size_t)p.k, p.lidx, p.n * (size_t)p.e);
+    }
+  };
+  if (zc) {
+    // Small call: the kernels read the survivors and indices from, and
+    // write their output to, pinned host memory (no DMA copies); the status
+    // word rides in the slot.
+    const Wave& w = waves[0];
+    if (int rc = ensure_slots(c, 0, hslot + 64)) return rc;
+    if (int rc = ensure_tabs(c, rows)) return rc;
+    uint8_t* h = c->h_slot[0];
+    uint32_t* h_st = reinterpret_cast<uint32_t*>(h + ((hslot + 3) & ~(size_t)3));
+    *h_st = 0;
+    stage_idx(w, h_idx(w, h));
+    if (!pinned)
+      for (size_t i : w.ids) par_memcpy(c, h + ch[i].o_in, ch[i].p.surv, ch[i].in);
+    if (int rc = launch_rebuild_pieces(c, staged(w, h, h_idx(w, h), pinned),
+                                       reinterpret_cast<uint8_t*>(c->d_tabs), c->sk, h_st))
+      return rc;
+    HIPCHK(hipStreamSynchronize(c->sk));
+    if (!pinned)
+      for (size_t i : w.ids) par_memcpy(c, ch[i].p.out, h + ch[i].o_out, ch[i].out);
+    return deferred_rc(c, __atomic_load_n(h_st, __ATOMIC_ACQUIRE));
+  }
+  if (int rc = ensure_slots(c, slot, hslot)) return rc;
+  if (int rc = ensure_tabs(c, kSlots * rows)) return rc;
+  const int rc = run_waves(
+      c, waves.size(),
+      [&](int s, size_t wi, hipStream_t st) -> int {
+        const Wave& w = waves[wi];
+        uint8_t* h = c->h_slot[s];
+        uint8_t* d = c->d_slot[s];
+        stage_idx(w, h_idx(w, h));
+        if (w.idx)
+          HIPCHK(hipMemcpyAsync(d + w.in + w.out, h_idx(w, h), w.idx, hipMemcpyHostToDevice, st));
+        for (size_t i : w.ids) {
+          if (pinned) {
+            HIPCHK(hipMemcpyAsync(d + ch[i].o_in, ch[i].p.surv, ch[i].in, hipMemcpyHostToDevice, st));
+          } else {
+            par_memcpy(c, h + ch[i].o_in, ch[i].p.surv, ch[i].in);
+          }
+        }
+        if (!pinned) HIPCHK(hipMemcpyAsync(d, h, w.in, hipMemcpyHostToDevice, st));
+        return MEMO_EC_OK;
+      },
+      [&](int s, size_t wi, hipStream_t st) -> int {
+        const Wave& w = waves[wi];
+        uint8_t* d = c->d_slot[s];
+        return launch_rebuild_pieces(c, staged(w, d, d + w.in + w.out, false),
+                                     reinterpret_cast<uint8_t*>(c->d_tabs) + (size_t)s * rows, st,
+                                     c->d_status + kStatusPipeline);
+      },
+      [&](int s, size_t wi, hipStream_t st) -> int {
+        const Wave& w = waves[wi];
+        uint8_t* d = c->d_slot[s];
+        if (pinned) {
+          for (size_t i : w.ids)
+            HIPCHK(hipMemcpyAsync(ch[i].p.out, d + ch[i].o_out, ch[i].out, hipMemcpyDeviceToHost, st));
+        } else {
+          HIPCHK(hipMemcpyAsync(c->h_slot[s] + w.in, d + w.in, w.out, hipMemcpyDeviceToHost, st));
+        }
+        // the deferred-error word rides behind the last wave's output, so
+        // reading it costs no extra round trip
+        if (wi + 1 == waves.size())
+          HIPCHK(hipMemcpyAsync(c->h_status, c->d_status + kStatusPipeline, sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, st));
+        return MEMO_EC_OK;
+      },
+      [&](int s, size_t wi) {
+        if (pinned) return;
+        for (size_t i : waves[wi].ids) par_memcpy(c, ch[i].p.out, c->h_slot[s] + ch[i].o_out, ch[i].out);
+      });
+  if (rc) return rc;
+  const uint32_t st = *c->h_status;
+  if (st) {
+    HIPCHK(hipMemsetAsync(c->d_status + kStatusPipeline, 0, sizeof(uint32_t), c->sd));
+    HIPCHK(hipStreamSynchronize(c->sd));
+  }
+  return deferred_rc(c, st);
 }
 
 }  // namespace
@@ -1521,9 +1678,7 @@ int memo_ec_stream_probe(memo_ec_ctx* c, int kin, int r, size_t S, size_t n, con
   DeviceGuard g(c->device);
   // the encode's geometry for (k, m) = (kin, r), launched as the probe
   const int R = mac_rbound(r), KC = mac_kchunk(kin, R);
-  const size_t step = max_blocks_per_launch(c, S);
-  for (size_t b0 = 0; b0 < n; b0 += step) {
-    const size_t cnt = std::min(step, n - b0);
+  return launch_spans(c, S, n, [&](size_t b0, size_t cnt) {
     Plan p = plan_segment((uint32_t)kin, (uint32_t)r, S, cnt, in + b0 * (size_t)kin * S,
                           (uint64_t)kin * S, S, out + b0 * (size_t)r * S, (uint64_t)r * S, S,
                           nullptr, 0, KC, R);
@@ -1531,9 +1686,8 @@ int memo_ec_stream_probe(memo_ec_ctx* c, int kin, int r, size_t S, size_t n, con
     p.lds = 0;
     p.seg.probe = (uint32_t)mode;
     std::vector<Plan> plans{p};
-    if (int rc = launch_plans(c, plans, c->stream)) return rc;
-  }
-  return MEMO_EC_OK;
+    return launch_plans(c, plans, c->stream);
+  });
 }
 
 #ifdef MEMO_EC_PERM_PROBE
@@ -1578,30 +1732,8 @@ int memo_ec_rebuild_uniform(memo_ec_ctx* c, int k, int m, size_t S, size_t n,
                             const uint8_t* surv_idx, const uint8_t* surv, const uint8_t* lost_idx,
                             int e, uint8_t* out, int where) {
   if (!c) return MEMO_EC_EINVAL;
-  if (int rc = check_km(k, m)) return rc;
-  if (e < 0 || e > m) return MEMO_EC_EINVAL;
-  if (e == 0 || n == 0) return MEMO_EC_OK;
-  if (S == 0 || S % 64 != 0 || !surv_idx || !surv || !lost_idx || !out) return MEMO_EC_EINVAL;
-  if (S >= kMaxShard || too_big(n, (size_t)(k + e) * S + k + e)) return MEMO_EC_ERANGE;
-  DeviceGuard g(c->device);
-  const int R = mac_rbound(e), KC = mac_kchunk(k, R);
-  const uint32_t* tab = nullptr;
-  ++c->call_seq;
-  if (int rc = pattern_tables(c, k, m, surv_idx, lost_idx, e, R, KC, &tab)) return rc;
-  auto run = [&](const uint8_t* src, uint8_t* dst, size_t cnt, hipStream_t st) -> int {
-    const size_t step = max_blocks_per_launch(c, S);
-    for (size_t b0 = 0; b0 < cnt; b0 += step) {
-      const size_t bc = std::min(step, cnt - b0);
-      std::vector<Plan> plans{plan_segment((uint32_t)k, (uint32_t)e, S, bc, src + b0 * (size_t)k * S,
-                                           (uint64_t)k * S, S, dst + b0 * (size_t)e * S,
-                                           (uint64_t)e * S, S, tab, 0, KC, R)};
-      if (int rc = launch_plans(c, plans, st)) return rc;
-    }
-    return MEMO_EC_OK;
-  };
-  if (where == MEMO_EC_DEVICE) return run(surv, out, n, c->stream);
-  if (where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
-  return host_mac(c, n, (size_t)k * S, (size_t)e * S, surv, out, where == MEMO_EC_HOST_PINNED, run);
+  const memo_ec_rebuild_segment seg{k, m, S, n, surv_idx, surv, lost_idx, e, 1, out};
+  return rebuild_segments_impl(c, 1, &seg, where);
 }
 
 int memo_ec_decode_rows(memo_ec_ctx* c, int k, int m, size_t n, const uint8_t* surv_idx,
@@ -1624,120 +1756,8 @@ int memo_ec_rebuild_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n,
                           const uint8_t* surv_idx, const uint8_t* surv, const uint8_t* lost_idx,
                           int e, uint8_t* out, int where) {
   if (!c) return MEMO_EC_EINVAL;
-  if (int rc = check_km(k, m)) return rc;
-  if (e < 0 || e > m) return MEMO_EC_EINVAL;
-  if (e == 0 || n == 0) return MEMO_EC_OK;
-  if (S == 0 || S % 64 != 0 || !surv_idx || !surv || !lost_idx || !out) return MEMO_EC_EINVAL;
-  if (S >= kMaxShard || too_big(n, (size_t)(k + e) * S + k + e)) return MEMO_EC_ERANGE;
-  DeviceGuard g(c->device);
-  const bool fused = rebuild_fused(c, n * (size_t)k * S);
-  if (where == MEMO_EC_DEVICE) {
-    if (int rc = ensure_tabs(c, rebuild_scratch(c, k, e, S, n, fused))) return rc;
-    if (int rc = rebuild_device(c, k, m, S, n, surv_idx, surv, lost_idx, e, out, fused, c->d_tabs,
-                                c->stream, c->d_status + kStatusDevice))
-      return rc;
-    // marks the scratch busy until this rebuild is done (host calls check it)
-    return hip_rc(hipEventRecord(c->ev_order, c->stream));
-  }
-  if (where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
-
-  const size_t in_b = (size_t)k * S, out_b = (size_t)e * S;
-  const size_t idx_b = (size_t)k + e;
-  const bool pinned = where == MEMO_EC_HOST_PINNED;
-  // device rebuilds still pending on the ctx stream read the same scratch
-  const hipError_t q = hipEventQuery(c->ev_order);
-  if (q == hipErrorNotReady) {
-    HIPCHK(hipStreamWaitEvent(c->sk, c->ev_order, 0));
-  } else if (q != hipSuccess) {
-    return hip_rc(q);
-  }
-  if (n * (in_b + out_b + idx_b) + 4 <= zc_max_bytes(c)) {
-    // Small call: decode and MAC run on pinned host memory directly (the
-    // survivors, indices and output in the bounce slot, or the caller's
-    // pinned buffers); the status word rides in the slot too.
-    const size_t slot = n * (in_b + out_b + idx_b) + 64;
-    if (int rc = ensure_slots(c, 0, slot)) return rc;
-    if (int rc = ensure_tabs(c, rebuild_scratch(c, k, e, S, n, fused))) return rc;
-    uint8_t* h = c->h_slot[0];
-    uint8_t* h_sidx = h + n * (in_b + out_b);
-    uint8_t* h_lidx = h_sidx + n * k;
-    uint32_t* h_st = reinterpret_cast<uint32_t*>(h + ((n * (in_b + out_b + idx_b) + 3) & ~(size_t)3));
-    std::memcpy(h_sidx, surv_idx, n * k);
-    std::memcpy(h_lidx, lost_idx, n * e);
-    *h_st = 0;
-    const uint8_t* sv = surv;
-    uint8_t* ov = out;
-    if (!pinned) {
-      par_memcpy(c, h, surv, n * in_b);
-      sv = h;
-      ov = h + n * in_b;
-    }
-    if (int rc = rebuild_device(c, k, m, S, n, h_sidx, sv, h_lidx, e, ov, fused, c->d_tabs, c->sk,
-                                h_st))
-      return rc;
-    HIPCHK(hipStreamSynchronize(c->sk));
-    if (!pinned) par_memcpy(c, out, ov, n * out_b);
-    int drc = c->deferred;
-    c->deferred = 0;
-    if (drc == MEMO_EC_OK && (__atomic_load_n(h_st, __ATOMIC_ACQUIRE) & 1u)) drc = MEMO_EC_ESINGULAR;
-    return drc;
-  }
-  size_t nb = std::max<size_t>(1, c->opt.pipe_bytes / in_b);
-  nb = std::min(nb, n);
-  // slot layout: [surv nb*in_b | out nb*out_b | surv_idx nb*k | lost_idx nb*e];
-  // pinned callers' data moves by DMA from their own buffers, so their host
-  // slot holds the indices only (no pinned bounce buffers of the batch size)
-  const size_t slot = nb * (in_b + out_b + idx_b);
-  const size_t hshift = pinned ? nb * (in_b + out_b) : 0;  // host slot offset of the device layout
-  if (int rc = ensure_slots(c, slot, slot - hshift)) return rc;
-  const size_t tabs = rebuild_scratch(c, k, e, S, nb, fused);
-  if (int rc = ensure_tabs(c, kSlots * tabs)) return rc;
-  const size_t o_out = nb * in_b, o_sidx = o_out + nb * out_b, o_lidx = o_sidx + nb * k;
-  const int rc = run_pipeline(
-      c, n, nb,
-      [&](int s, size_t b0, size_t cnt, hipStream_t st) -> int {
-        uint8_t* h = c->h_slot[s];
-        uint8_t* d = c->d_slot[s];
-        std::memcpy(h + o_sidx - hshift, surv_idx + b0 * k, cnt * k);  // indices: always bounced
-        std::memcpy(h + o_lidx - hshift, lost_idx + b0 * e, cnt * e);
-        HIPCHK(hipMemcpyAsync(d + o_sidx, h + o_sidx - hshift, nb * idx_b, hipMemcpyHostToDevice, st));
-        const uint8_t* src = surv + b0 * in_b;
-        if (!pinned) {
-          par_memcpy(c, h, src, cnt * in_b);
-          src = h;
-        }
-        return hip_rc(hipMemcpyAsync(d, src, cnt * in_b, hipMemcpyHostToDevice, st));
-      },
-      [&](int s, size_t, size_t cnt, hipStream_t st) -> int {
-        uint8_t* d = c->d_slot[s];
-        return rebuild_device(c, k, m, S, cnt, d + o_sidx, d, d + o_lidx, e, d + o_out, fused,
-                              reinterpret_cast<uint8_t*>(c->d_tabs) + (size_t)s * tabs, st,
-                              c->d_status + kStatusPipeline);
-      },
-      [&](int s, size_t b0, size_t cnt, hipStream_t st) -> int {
-        uint8_t* dst = pinned ? out + b0 * out_b : c->h_slot[s] + o_out;
-        HIPCHK(hipMemcpyAsync(dst, c->d_slot[s] + o_out, cnt * out_b, hipMemcpyDeviceToHost, st));
-        // the deferred-error word rides behind the last batch's output, so
-        // reading it costs no extra round trip
-        if (b0 + cnt == n)
-          HIPCHK(hipMemcpyAsync(c->h_status, c->d_status + kStatusPipeline, sizeof(uint32_t),
-                                hipMemcpyDeviceToHost,
-                                st));
-        return MEMO_EC_OK;
-      },
-      [&](int s, size_t b0, size_t cnt) {
-        if (!pinned) par_memcpy(c, out + b0 * out_b, c->h_slot[s] + o_out, cnt * out_b);
-      });
-  if (rc) return rc;
-  const uint32_t st = *c->h_status;
-  if (st) {
-    HIPCHK(hipMemsetAsync(c->d_status + kStatusPipeline, 0, sizeof(uint32_t), c->sd));
-    HIPCHK(hipStreamSynchronize(c->sd));
-  }
-  int drc = c->deferred;
-  c->deferred = 0;
-  if (drc == MEMO_EC_OK && (st & 1u)) drc = MEMO_EC_ESINGULAR;
-  return drc;
+  const memo_ec_rebuild_segment seg{k, m, S, n, surv_idx, surv, lost_idx, e, 0, out};
+  return rebuild_segments_impl(c, 1, &seg, where);
 }
 
 int memo_ec_encode_segments(memo_ec_ctx* c, int nseg, const memo_ec_segment* segs) {
@@ -1793,204 +1813,7 @@ int memo_ec_rebuild_segments(memo_ec_ctx* c, int nseg, const memo_ec_rebuild_seg
   if (!c || nseg < 0 || nseg > MEMO_EC_MAX_REBUILD_SEGMENTS || (nseg && !segs)) return MEMO_EC_EINVAL;
   if (where != MEMO_EC_DEVICE && where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED)
     return MEMO_EC_EINVAL;
-  DeviceGuard g(c->device);
-  std::vector<RPiece> ps;
-  if (int rc = plan_rebuild_segments(c, nseg, segs, ps)) return rc;
-  if (ps.empty()) return MEMO_EC_OK;
-  if (where == MEMO_EC_DEVICE) {
-    if (int rc = ensure_tabs(c, rows_scratch(ps))) return rc;
-    if (int rc = launch_rebuild_pieces(c, ps, reinterpret_cast<uint8_t*>(c->d_tabs), c->stream,
-                                       c->d_status + kStatusDevice))
-      return rc;
-    // marks the scratch busy until these rebuilds are done (host calls check it)
-    return hip_rc(hipEventRecord(c->ev_order, c->stream));
-  }
-  const bool pinned = where == MEMO_EC_HOST_PINNED;
-  // device rebuilds still pending on the ctx stream read the same scratch
-  const hipError_t q = hipEventQuery(c->ev_order);
-  if (q == hipErrorNotReady) {
-    HIPCHK(hipStreamWaitEvent(c->sk, c->ev_order, 0));
-  } else if (q != hipSuccess) {
-    return hip_rc(q);
-  }
-  // Chunks of at most one pipeline batch of survivors, packed in order into
-  // waves of at most one batch; a wave's slot holds [survivors | outputs |
-  // per-block indices].
-  struct Chunk {
-    RPiece p;  // host pointers
-    size_t in, out, idx;
-    size_t o_in = 0, o_out = 0, o_idx = 0;
-  };
-  std::vector<Chunk> ch;
-  const size_t pipe = c->opt.pipe_bytes;
-  size_t total = 0;
-  for (const RPiece& p : ps) {
-    const size_t in_b = (size_t)p.k * p.S, out_b = (size_t)p.e * p.S;
-    const bool uni = p.mode == MAC_ENCODE;
-    const size_t per = std::max<size_t>(1, pipe / in_b);
-    for (size_t b0 = 0; b0 < p.n; b0 += per) {
-      Chunk x;
-      x.p = p;
-      x.p.b0 = b0;
-      x.p.n = std::min(per, p.n - b0);
-      x.p.surv = p.surv + b0 * in_b;
-      x.p.out = p.out + b0 * out_b;
-      if (!uni) {
-        x.p.sidx = p.sidx + b0 * (size_t)p.k;
-        x.p.lidx = p.lidx + b0 * (size_t)p.e;
-      }
-      x.in = x.p.n * in_b;
-      x.out = x.p.n * out_b;
-      x.idx = uni ? 0 : x.p.n * (size_t)(p.k + p.e);
-      total += x.in + x.out + x.idx;
-      ch.push_back(x);
-    }
-  }
-  struct Wave {
-    std::vector<size_t> ids;
-    size_t in = 0, out = 0, idx = 0;
-  };
-  std::vector<Wave> waves;
-  const bool zc = total + 64 <= zc_max_bytes(c);
-  for (size_t i = 0; i < ch.size(); ++i) {
-    if (waves.empty() || (!zc && waves.back().in + ch[i].in > pipe)) waves.emplace_back();
-    Wave& w = waves.back();
-    w.ids.push_back(i);
-    w.in += ch[i].in;
-    w.out += ch[i].out;
-    w.idx += ch[i].idx;
-  }
-  size_t slot = 0, rows = 0;
-  for (Wave& w : waves) {
-    size_t oi = 0, oo = w.in, ox = w.in + w.out;
-    for (size_t i : w.ids) {
-      ch[i].o_in = oi;
-      ch[i].o_out = oo;
-      ch[i].o_idx = ox;
-      oi += ch[i].in;
-      oo += ch[i].out;
-      ox += ch[i].idx;
-    }
-    slot = std::max(slot, w.in + w.out + w.idx);
-    std::vector<RPiece> wp;
-    for (size_t i : w.ids) wp.push_back(ch[i].p);
-    rows = std::max(rows, rows_scratch(wp));  // decode rows + table images (256-byte multiple)
-  }
-  // the pieces as the kernels see them, in slot memory at base (surv / out
-  // at the caller's pinned buffers when pinned_io)
-  auto staged = [&](const Wave& w, uint8_t* base, bool pinned_io) {
-    std::vector<RPiece> dp;
-    for (size_t i : w.ids) {
-      RPiece p = ch[i].p;
-      if (!pinned_io) {
-        p.surv = base + ch[i].o_in;
-        p.out = base + ch[i].o_out;
-      }
-      if (p.mode != MAC_ENCODE) {
-        p.sidx = base + ch[i].o_idx;
-        p.lidx = base + ch[i].o_idx + p.n * (size_t)p.k;
-      }
-      dp.push_back(p);
-    }
-    return dp;
-  };
-  // indices staged at their slot offsets less `shift` (pinned pipeline
-  // calls keep only the indices in their host slot)
-  auto stage_idx = [&](const Wave& w, uint8_t* h, size_t shift = 0) {
-    for (size_t i : w.ids) {
-      const RPiece& p = ch[i].p;
-      if (p.mode == MAC_ENCODE) continue;
-      std::memcpy(h + ch[i].o_idx - shift, p.sidx, p.n * (size_t)p.k);
-      std::memcpy(h + ch[i].o_idx - shift + p.n * (size_t)p.k, p.lidx, p.n * (size_t)p.e);
-    }
-  };
-  if (zc) {
-    // Small call: the kernels read the survivors and indices from, and
-    // write their output to, pinned host memory (no DMA copies); the status
-    // word rides in the slot.
-    const Wave& w = waves[0];
-    if (int rc = ensure_slots(c, 0, slot + 64)) return rc;
-    if (int rc = ensure_tabs(c, rows)) return rc;
-    uint8_t* h = c->h_slot[0];
-    uint32_t* h_st = reinterpret_cast<uint32_t*>(h + ((slot + 3) & ~(size_t)3));
-    *h_st = 0;
-    stage_idx(w, h);
-    if (!pinned)
-      for (size_t i : w.ids) par_memcpy(c, h + ch[i].o_in, ch[i].p.surv, ch[i].in);
-    if (int rc = launch_rebuild_pieces(c, staged(w, h, pinned), reinterpret_cast<uint8_t*>(c->d_tabs),
-                                       c->sk, h_st))
-      return rc;
-    HIPCHK(hipStreamSynchronize(c->sk));
-    if (!pinned)
-      for (size_t i : w.ids) par_memcpy(c, ch[i].p.out, h + ch[i].o_out, ch[i].out);
-    int drc = c->deferred;
-    c->deferred = 0;
-    if (drc == MEMO_EC_OK && (__atomic_load_n(h_st, __ATOMIC_ACQUIRE) & 1u)) drc = MEMO_EC_ESINGULAR;
-    return drc;
-  }
-  // pinned: the survivors and outputs move by DMA from the caller's
-  // buffers, and the host slot holds a wave's indices only
-  size_t hslot = slot;
-  if (pinned) {
-    hslot = 64;
-    for (const Wave& w : waves) hslot = std::max(hslot, w.idx);
-  }
-  if (int rc = ensure_slots(c, slot, hslot)) return rc;
-  if (int rc = ensure_tabs(c, kSlots * rows)) return rc;
-  const int rc = run_waves(
-      c, waves.size(),
-      [&](int s, size_t wi, hipStream_t st) -> int {
-        const Wave& w = waves[wi];
-        uint8_t* h = c->h_slot[s];
-        uint8_t* d = c->d_slot[s];
-        const size_t shift = pinned ? w.in + w.out : 0;
-        stage_idx(w, h, shift);
-        if (w.idx)
-          HIPCHK(hipMemcpyAsync(d + w.in + w.out, h + w.in + w.out - shift, w.idx, hipMemcpyHostToDevice, st));
-        for (size_t i : w.ids) {
-          if (pinned) {
-            HIPCHK(hipMemcpyAsync(d + ch[i].o_in, ch[i].p.surv, ch[i].in, hipMemcpyHostToDevice, st));
-          } else {
-            par_memcpy(c, h + ch[i].o_in, ch[i].p.surv, ch[i].in);
-          }
-        }
-        if (!pinned) HIPCHK(hipMemcpyAsync(d, h, w.in, hipMemcpyHostToDevice, st));
-        return MEMO_EC_OK;
-      },
-      [&](int s, size_t wi, hipStream_t st) -> int {
-        return launch_rebuild_pieces(c, staged(waves[wi], c->d_slot[s], false),
-                                     reinterpret_cast<uint8_t*>(c->d_tabs) + (size_t)s * rows, st,
-                                     c->d_status + kStatusPipeline);
-      },
-      [&](int s, size_t wi, hipStream_t st) -> int {
-        const Wave& w = waves[wi];
-        uint8_t* d = c->d_slot[s];
-        if (pinned) {
-          for (size_t i : w.ids)
-            HIPCHK(hipMemcpyAsync(ch[i].p.out, d + ch[i].o_out, ch[i].out, hipMemcpyDeviceToHost, st));
-        } else {
-          HIPCHK(hipMemcpyAsync(c->h_slot[s] + w.in, d + w.in, w.out, hipMemcpyDeviceToHost, st));
-        }
-        // the deferred-error word rides behind the last wave's output
-        if (wi + 1 == waves.size())
-          HIPCHK(hipMemcpyAsync(c->h_status, c->d_status + kStatusPipeline, sizeof(uint32_t),
-                                hipMemcpyDeviceToHost, st));
-        return MEMO_EC_OK;
-      },
-      [&](int s, size_t wi) {
-        if (pinned) return;
-        for (size_t i : waves[wi].ids) par_memcpy(c, ch[i].p.out, c->h_slot[s] + ch[i].o_out, ch[i].out);
-      });
-  if (rc) return rc;
-  const uint32_t st = *c->h_status;
-  if (st) {
-    HIPCHK(hipMemsetAsync(c->d_status + kStatusPipeline, 0, sizeof(uint32_t), c->sd));
-    HIPCHK(hipStreamSynchronize(c->sd));
-  }
-  int drc = c->deferred;
-  c->deferred = 0;
-  if (drc == MEMO_EC_OK && (st & 1u)) drc = MEMO_EC_ESINGULAR;
-  return drc;
+  return rebuild_segments_impl(c, nseg, segs, where);
 }
 
 int memo_ec_sha256_batch(memo_ec_ctx* c, size_t n, const uint8_t* prefix, size_t prefix_len,
