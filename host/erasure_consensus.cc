@@ -14,8 +14,6 @@
 
 namespace memo_host {
 
-namespace {
-
 // MEMO_EC_PLUGIN_TIMING=1: per-phase wall times of the batched paths on
 // stderr (profiling the host side; off by default).
 struct PhaseTimer {
@@ -43,6 +41,7 @@ struct PhaseTimer {
   }
 };
 
+namespace {
 // Block payload d as k shards of Sb bytes into k slots of S >= Sb bytes at
 // dst (memo_ec_shard_size padding and the slot tails zeroed).
 void copy_padded(const Buffer& d, int k, size_t Sb, uint8_t* dst, size_t S) {
@@ -69,6 +68,59 @@ void check(int rc, const char* what) {
   if (rc != MEMO_EC_OK) throw Error(std::string("memo_ec ") + what + ": " + memo_ec_strerror(rc));
 }
 }  // namespace
+
+// ------------------------------------------------------- rebuild planning
+std::vector<RebuildBatch> plan_rebuild_batches(const std::vector<RebuildItem>& items, int k,
+                                               int batch_max, int uniform_min,
+                                               size_t uniform_min_bytes) {
+  // keyed by (S bucket, the item itself: its k + e pattern bytes as a string)
+  using Key = std::pair<int, const RebuildItem*>;
+  auto less = [k](const Key& a, const Key& b) {
+    if (a.first != b.first) return a.first < b.first;
+    return std::lexicographical_compare(a.second->pat, a.second->pat + k + a.second->e, b.second->pat,
+                                        b.second->pat + k + b.second->e);
+  };
+  std::map<Key, std::vector<size_t>, decltype(less)> by_pat(less);
+  for (size_t i = 0; i < items.size(); ++i) by_pat[{size_bucket(items[i].S), &items[i]}].push_back(i);
+  std::vector<RebuildBatch> batches;
+  auto cut = [&](int e, bool uniform, const std::vector<size_t>& ids) {
+    for (size_t b0 = 0; b0 < ids.size(); b0 += batch_max) {
+      const size_t b1 = std::min(ids.size(), b0 + (size_t)batch_max);
+      RebuildBatch b{e, uniform, 0, {}, {ids.begin() + b0, ids.begin() + b1}};
+      if (uniform) b.pat.assign(items[ids[0]].pat, items[ids[0]].pat + k + e);
+      for (size_t i : b.items) b.S = std::max(b.S, items[i].S);
+      batches.push_back(std::move(b));
+    }
+  };
+  std::map<std::pair<int, int>, std::vector<size_t>> rest;
+  for (auto& bp : by_pat) {
+    const int e = bp.first.second->e;
+    const size_t bytes = bp.second.size() * (size_t)k * ((size_t)64 << bp.first.first);
+    if ((int)bp.second.size() >= uniform_min && bytes >= uniform_min_bytes) {
+      cut(e, true, bp.second);
+    } else {
+      auto& r = rest[{bp.first.first, e}];
+      r.insert(r.end(), bp.second.begin(), bp.second.end());
+    }
+  }
+  for (auto& r : rest) cut(r.first.second, false, r.second);
+  return batches;
+}
+
+std::vector<size_t> cut_rebuild_chunks(const std::vector<RebuildBatch>& batches, int k, size_t limit) {
+  std::vector<size_t> cuts{0};
+  size_t acc = 0;
+  for (size_t x = 0; x < batches.size(); ++x) {
+    const size_t sb = batches[x].items.size() * k * batches[x].S;
+    if (acc > 0 && acc + sb > limit) {
+      cuts.push_back(x);
+      acc = 0;
+    }
+    acc += sb;
+  }
+  if (cuts.back() != batches.size()) cuts.push_back(batches.size());
+  return cuts;
+}
 
 // ------------------------------------------------------------------ codec
 Codec::Codec(int device, int contexts) {
@@ -853,21 +905,15 @@ void ErasureConsensus::batcher_loop() {
     std::map<int, std::vector<EncodeJob*>> by_s;
     for (auto* j : jobs) by_s[size_bucket(memo_ec_shard_size(j->block->data.size(), o_.k))].push_back(j);
     for (auto& g : by_s) {
-      const size_t n = g.second.size();
-      size_t S = 0;
-      for (auto* j : g.second) S = std::max(S, memo_ec_shard_size(j->block->data.size(), o_.k));
+      std::vector<const Block*> bs;
+      for (auto* j : g.second) bs.push_back(j->block);
       try {
-        auto data = arena_.lease(n * o_.k * S), parity = arena_.lease(n * o_.m * S);
-        for (size_t i = 0; i < n; ++i) {
-          const auto& d = g.second[i]->block->data;
-          copy_padded(d, o_.k, memo_ec_shard_size(d.size(), o_.k), data.data() + i * o_.k * S, S);
-        }
-        codec_.encode(o_.k, o_.m, S, n, data.data(), parity.data(), data.pinned() && parity.pinned());
-        for (size_t i = 0; i < n; ++i) {
-          const size_t Sb = memo_ec_shard_size(g.second[i]->block->data.size(), o_.k);
+        const Encoded enc = encode_bucket(bs, false, nullptr);
+        for (size_t i = 0; i < bs.size(); ++i) {
+          const size_t Sb = memo_ec_shard_size(bs[i]->data.size(), o_.k);
           Buffer p((size_t)o_.m * Sb);
           for (int r = 0; r < o_.m; ++r)
-            std::copy(parity.data() + (i * o_.m + r) * S, parity.data() + (i * o_.m + r) * S + Sb,
+            std::copy(enc.parity.data() + (i * o_.m + r) * enc.S, enc.parity.data() + (i * o_.m + r) * enc.S + Sb,
                       p.begin() + (size_t)r * Sb);
           g.second[i]->parity.set_value(std::move(p));
         }
@@ -876,6 +922,26 @@ void ErasureConsensus::batcher_loop() {
       }
     }
   }
+}
+
+ErasureConsensus::Encoded ErasureConsensus::encode_bucket(const std::vector<const Block*>& bs,
+                                                          bool on_pool, PhaseTimer* tm) {
+  const size_t n = bs.size();
+  size_t S = 0;
+  for (auto* b : bs) S = std::max(S, memo_ec_shard_size(b->data.size(), o_.k));
+  Encoded enc{arena_.lease(n * o_.k * S), arena_.lease(n * o_.m * S), S};
+  if (tm) tm->lap("alloc");
+  auto copy_in = [&](size_t i) {
+    const auto& d = bs[i]->data;
+    copy_padded(d, o_.k, memo_ec_shard_size(d.size(), o_.k), enc.data.data() + i * o_.k * S, S);
+  };
+  if (on_pool) pool_.parallel_for(n, copy_in);
+  else
+    for (size_t i = 0; i < n; ++i) copy_in(i);
+  if (tm) tm->lap("copy_in");
+  codec_.encode(o_.k, o_.m, S, n, enc.data.data(), enc.parity.data(), enc.data.pinned() && enc.parity.pinned());
+  if (tm) tm->lap("encode");
+  return enc;
 }
 
 // Send shard i to owner i (send_immutable_block's fan-out, Paxos.cc:324-360):
@@ -1078,24 +1144,13 @@ void ErasureConsensus::store_many(const std::vector<Block>& blocks) {
       by_s[size_bucket(memo_ec_shard_size(b->data.size(), o_.k))].push_back(b);
     }
     for (auto& g : by_s) {
-      const size_t n = g.second.size();
-      size_t S = 0;
-      for (auto* b : g.second) S = std::max(S, memo_ec_shard_size(b->data.size(), o_.k));
-      auto data = arena_.lease(n * o_.k * S), parity = arena_.lease(n * o_.m * S);
-      tm.lap("alloc");
-      pool_.parallel_for(n, [&](size_t i) {
-        const auto& d = g.second[i]->data;
-        copy_padded(d, o_.k, memo_ec_shard_size(d.size(), o_.k), data.data() + i * o_.k * S, S);
-      });
-      tm.lap("copy_in");
-      codec_.encode(o_.k, o_.m, S, n, data.data(), parity.data(), data.pinned() && parity.pinned());
-      tm.lap("encode");
+      const Encoded enc = encode_bucket(g.second, true, &tm);
       // shards straight from the batch buffers (a block's shard is the first
       // Sb bytes of its S-byte slot)
       // the shards go out on the pool; the batch's placements then enter
       // the index under one lock (also when some block fell short)
-      std::vector<Placed> placed(n);
-      std::exception_ptr err = place_batch(g.second, data.data(), parity.data(), S, placed);
+      std::vector<Placed> placed(g.second.size());
+      std::exception_ptr err = place_batch(g.second, enc.data.data(), enc.parity.data(), enc.S, placed);
       tm.lap("place");
       commit_placements(placed);
       tm.lap("index");
@@ -1116,7 +1171,8 @@ void ErasureConsensus::store_many(const std::vector<Block>& blocks) {
 // With `block`, the payloads of data shards are validated on the silo's
 // view and copied straight into their slots of *block (k x S, allocated on
 // the first accepted shard); their entries in the result carry no bytes.
-// Parity shards always come back whole (header + payload).
+// Parity shards always come back whole (header + payload).  The result is
+// in ascending order of shard index.
 std::vector<std::pair<int, Buffer>> ErasureConsensus::gather_shards(const Address& a, int want,
                                                                     bool& any_down,
                                                                     ShardHeader* hdr,
@@ -1305,9 +1361,7 @@ ErasureConsensus::Gathered ErasureConsensus::collect(const Address& a, bool para
     if ((int)g.shards.size() < k)
       throw TooFewPeers("erasure: " + std::to_string(g.shards.size()) +
                         " shards reachable, need " + std::to_string(k));
-    std::sort(g.shards.begin(), g.shards.end(),
-              [](const auto& x, const auto& y) { return x.first < y.first; });
-    g.shards.resize(k);  // data shards first (sorted), then parity
+    g.shards.resize(k);  // data shards first, then parity: gather_shards returns them in index order
     std::vector<bool> have(k, false);
     for (auto& s : g.shards)
       if (s.first < k) have[s.first] = true;
@@ -1344,24 +1398,28 @@ std::unique_ptr<Block> ErasureConsensus::assemble(const Address& a, Gathered& g,
   return b;
 }
 
+Buffer ErasureConsensus::rebuild_one(size_t S, const std::vector<ShardRef>& from,
+                                     const std::vector<uint8_t>& lost) {
+  std::vector<uint8_t> sidx;
+  Buffer surv(from.size() * S), out(lost.size() * S);
+  for (const ShardRef& sh : from) {
+    std::memcpy(surv.data() + sidx.size() * S, sh.second, S);
+    sidx.push_back((uint8_t)sh.first);
+  }
+  codec_.rebuild(o_.k, o_.m, S, 1, sidx.data(), surv.data(), lost.data(), (int)lost.size(), out.data());
+  return out;
+}
+
 std::unique_ptr<Block> ErasureConsensus::_fetch(Address a, std::optional<int> local_version) {
   if (a.mutable_block()) return backend_->fetch(a, local_version);
-  const int k = o_.k;
   Gathered g = collect(a, true);
   if (g.err) std::rethrow_exception(g.err);
   Buffer out;
   if (!g.lost.empty()) {
     // systematic shards missing: rebuild them from the k survivors (GPU)
-    const size_t S = g.h.shard_size;
-    std::vector<uint8_t> sidx(k);
-    Buffer surv((size_t)k * S);
-    for (int s = 0; s < k; ++s) {
-      sidx[s] = (uint8_t)g.shards[s].first;
-      std::memcpy(surv.data() + (size_t)s * S, g.payload(s), S);
-    }
-    out.resize(g.lost.size() * S);
-    codec_.rebuild(k, o_.m, S, 1, sidx.data(), surv.data(), g.lost.data(), (int)g.lost.size(),
-                   out.data());
+    std::vector<ShardRef> surv;
+    for (size_t s = 0; s < g.shards.size(); ++s) surv.emplace_back(g.shards[s].first, g.payload(s));
+    out = rebuild_one(g.h.shard_size, surv, g.lost);
     ++decoded_;
   }
   try {
@@ -1473,34 +1531,32 @@ std::unique_ptr<Block> ErasureConsensus::recover_from(const Address& a, int want
   bool any_down = false;
   ShardHeader h;
   std::vector<Node*> from(total, nullptr);
-  auto have = gather_shards(a, want, any_down, &h, parallel, &from);
-  std::sort(have.begin(), have.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+  const auto have = gather_shards(a, want, any_down, &h, parallel, &from);
   const int n = (int)have.size();
   if (n <= k) {
     if (want < total) return nullptr;  // the wider gather may find more
     throw AddressMismatch(what + " (no spare shard to try)");
   }
   const size_t S = h.shard_size;
-  std::vector<uint8_t> sidx(k), lost;
-  Buffer surv((size_t)k * S), out((size_t)m * S), block;
+  std::vector<uint8_t> lost;
+  std::vector<ShardRef> picks(k);
+  Buffer block;
   for (const auto& sub : retry_subsets(n, k, o_.verify_subsets)) {
     std::vector<bool> present(k, false);
     block.assign((size_t)k * S, 0);
     for (int t = 0; t < k; ++t) {
       const auto& sh = have[sub[t]];
-      sidx[t] = (uint8_t)sh.first;
-      const uint8_t* pay = sh.second.data() + ShardHeader::kSize;
-      std::memcpy(surv.data() + (size_t)t * S, pay, S);
+      picks[t] = {sh.first, sh.second.data() + ShardHeader::kSize};
       if (sh.first < k) {
         present[sh.first] = true;
-        std::memcpy(block.data() + (size_t)sh.first * S, pay, S);
+        std::memcpy(block.data() + (size_t)sh.first * S, picks[t].second, S);
       }
     }
     lost.clear();
     for (int j = 0; j < k; ++j)
       if (!present[j]) lost.push_back((uint8_t)j);
     if (!lost.empty()) {
-      codec_.rebuild(k, m, S, 1, sidx.data(), surv.data(), lost.data(), (int)lost.size(), out.data());
+      const Buffer out = rebuild_one(S, picks, lost);
       for (size_t r = 0; r < lost.size(); ++r)
         std::memcpy(block.data() + (size_t)lost[r] * S, out.data() + r * S, S);
     }
@@ -1533,7 +1589,7 @@ std::unique_ptr<Block> ErasureConsensus::recover_from(const Address& a, int want
 // order.  The reference hands the whole batch over at once too
 // (Consensus::_fetch(vector<AddressVersion>), Consensus.cc:101-124).
 void ErasureConsensus::_fetch(const std::vector<AddressVersion>& request, ReceiveBlock res) {
-  const int k = o_.k, m = o_.m;
+  const int k = o_.k;
   const size_t n = request.size();
   std::vector<Address> addresses(n);
   for (size_t i = 0; i < n; ++i) addresses[i] = request[i].first;
@@ -1562,40 +1618,22 @@ void ErasureConsensus::_fetch(const std::vector<AddressVersion>& request, Receiv
     pool_.parallel_for(imm.size(), [&](size_t t) { g[imm[t]] = collect(addresses[imm[t]], false, true); });
   }
   tm.lap("gather");
-  // degraded blocks by (S bucket, erasure pattern); patterns shared by at
-  // least uniform_min blocks (a node down) take the uniform rebuild, the
-  // rest group by (S bucket, e) for the per-block rebuild
-  std::map<std::pair<int, std::vector<uint8_t>>, std::vector<size_t>> by_pat;
-  std::vector<size_t> direct;
+  // the degraded blocks are the planner's items (ids: their request slots)
+  std::vector<RebuildItem> items;
+  std::vector<size_t> ids, direct;
   for (size_t i : imm) {
     if (g[i].err) {
       errs[i] = g[i].err;
     } else if (g[i].lost.empty()) {
       direct.push_back(i);
     } else {
-      std::vector<uint8_t> pat;
-      for (auto& sh : g[i].shards) pat.push_back((uint8_t)sh.first);
-      pat.insert(pat.end(), g[i].lost.begin(), g[i].lost.end());
-      by_pat[{size_bucket(g[i].h.shard_size), std::move(pat)}].push_back(i);
+      RebuildItem it{(size_t)g[i].h.shard_size, (int)g[i].lost.size(), {}};
+      for (int s = 0; s < k; ++s) it.pat[s] = (uint8_t)g[i].shards[s].first;
+      std::copy(g[i].lost.begin(), g[i].lost.end(), it.pat + k);
+      items.push_back(it);
+      ids.push_back(i);
     }
   }
-  struct FGroup {
-    int e;
-    bool uniform;
-    std::vector<uint8_t> pat;
-    std::vector<size_t> ids;
-  };
-  std::vector<FGroup> groups;
-  std::map<std::pair<int, size_t>, std::vector<size_t>> rest;
-  for (auto& bp : by_pat) {
-    const int e = (int)(bp.first.second.size() - (size_t)k);
-    const size_t bytes = bp.second.size() * (size_t)k * ((size_t)64 << bp.first.first);
-    if ((int)bp.second.size() >= o_.uniform_min && bytes >= o_.uniform_min_bytes)
-      groups.push_back({e, true, bp.first.second, bp.second});
-    else rest[{bp.first.first, (size_t)e}].insert(rest[{bp.first.first, (size_t)e}].end(),
-                                                  bp.second.begin(), bp.second.end());
-  }
-  for (auto& r : rest) groups.push_back({(int)r.first.second, false, {}, r.second});
   auto finish = [&](size_t i, const uint8_t* rebuilt, size_t stride) {
     try {
       try {
@@ -1610,113 +1648,93 @@ void ErasureConsensus::_fetch(const std::vector<AddressVersion>& request, Receiv
   };
   pool_.parallel_for(direct.size(), [&](size_t t) { finish(direct[t], nullptr, 0); });
   tm.lap("assemble_direct");
-  // every group's batches staged, then ONE codec call for all of them
-  // (memo_ec_rebuild_segments: a segment per batch), then reassembly
-  struct FBatch {
-    const FGroup* grp;
-    size_t b0, nb, S;
-    std::vector<uint8_t> sidx, lidx;
-    uint8_t* surv = nullptr;  // this batch's part of the call's two leases
-    uint8_t* out = nullptr;
+  // at most stage_bytes of survivors staged at a time (a node-loss fetch of
+  // thousands of blocks does not pin GBs); reassembly as each chunk comes back
+  auto survivors = [&](size_t t, const uint8_t** p) {
+    for (int s = 0; s < k; ++s) p[s] = g[ids[t]].payload(s);
   };
-  std::vector<FBatch> batches;
-  for (auto& grp : groups)
-    for (size_t b0 = 0; b0 < grp.ids.size(); b0 += o_.batch_max) {
-      FBatch fb;
-      fb.grp = &grp;
-      fb.b0 = b0;
-      fb.nb = std::min<size_t>(o_.batch_max, grp.ids.size() - b0);
-      fb.S = 0;  // the batch's largest shard; smaller shards zero-padded
-      for (size_t bi = 0; bi < fb.nb; ++bi) fb.S = std::max(fb.S, (size_t)g[grp.ids[b0 + bi]].h.shard_size);
-      batches.push_back(std::move(fb));
-    }
-  // Chunks of batches with up to stage_bytes of survivors each: one
-  // survivor and one output lease per chunk, carved per batch (a lease per
-  // batch took a pinned allocation each beyond the arena's few kept buffers,
-  // ~2 ms apiece: 240 ms for 16,384 4 KiB blocks), and ONE codec call per
-  // chunk for all its batches (memo_ec_rebuild_segments: a segment per
-  // batch).  A node-loss fetch of thousands of degraded blocks so stages at
-  // most a chunk at a time instead of pinning GBs at once.
-  std::vector<size_t> cuts{0};
-  {
-    size_t acc = 0;
-    for (size_t x = 0; x < batches.size(); ++x) {
-      const size_t sb = batches[x].nb * k * batches[x].S;
-      if (acc > 0 && acc + sb > o_.stage_bytes) {
-        cuts.push_back(x);
-        acc = 0;
-      }
-      acc += sb;
-    }
-    if (cuts.back() != batches.size()) cuts.push_back(batches.size());
-  }
+  auto rebuilt = [&](size_t t, const uint8_t* shards, size_t stride) {
+    ++decoded_;
+    finish(ids[t], shards, stride);
+  };
+  stage_rebuilds(items, plan_rebuild_batches(items, k, o_.batch_max, o_.uniform_min, o_.uniform_min_bytes),
+                 o_.stage_bytes, survivors, nullptr, rebuilt, "assemble", tm);
+  for (size_t i = 0; i < n; ++i) res(addresses[i], std::move(blocks[i]), errs[i]);
+}
+
+size_t ErasureConsensus::stage_rebuilds(const std::vector<RebuildItem>& items,
+                                        const std::vector<RebuildBatch>& batches, size_t limit,
+                                        const Survivors& survivors, const std::function<void(size_t)>& staged,
+                                        const Rebuilt& rebuilt, const char* rebuilt_lap, PhaseTimer& tm) {
+  const int k = o_.k, m = o_.m;
+  const std::vector<size_t> cuts = cut_rebuild_chunks(batches, k, limit);
   for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
-    const size_t x0 = cuts[ci], x1 = cuts[ci + 1];
-    std::vector<size_t> o_surv(x1 - x0), o_out(x1 - x0);
+    const size_t nx = cuts[ci + 1] - cuts[ci];
+    const RebuildBatch* bs = batches.data() + cuts[ci];
+    std::vector<size_t> o_surv(nx), o_out(nx);             // each batch's part of the two leases
+    std::vector<std::vector<uint8_t>> sidx(nx), lidx(nx);  // per-block patterns (no uniform batch's)
+    std::vector<std::pair<size_t, size_t>> work;  // (batch, block) pairs for the pool
     size_t surv_bytes = 0, out_bytes = 0;
-    for (size_t x = x0; x < x1; ++x) {
-      o_surv[x - x0] = surv_bytes;
-      o_out[x - x0] = out_bytes;
-      surv_bytes += (batches[x].nb * k * batches[x].S + 63) & ~(size_t)63;
-      out_bytes += (batches[x].nb * batches[x].grp->e * batches[x].S + 63) & ~(size_t)63;
+    for (size_t x = 0; x < nx; ++x) {
+      const size_t nb = bs[x].items.size();
+      o_surv[x] = surv_bytes;
+      o_out[x] = out_bytes;
+      surv_bytes += (nb * k * bs[x].S + 63) & ~(size_t)63;
+      out_bytes += (nb * bs[x].e * bs[x].S + 63) & ~(size_t)63;
+      if (!bs[x].uniform) {
+        sidx[x].resize(nb * k);
+        lidx[x].resize(nb * bs[x].e);
+      }
+      for (size_t bi = 0; bi < nb; ++bi) work.emplace_back(x, bi);
     }
     PinnedArena::Lease surv_all = arena_.lease(surv_bytes), out_all = arena_.lease(out_bytes);
-    const bool pin = surv_all.pinned() && out_all.pinned();
-    for (size_t x = x0; x < x1; ++x) {
-      FBatch& fb = batches[x];
-      const int e = fb.grp->e;
-      fb.surv = surv_all.data() + o_surv[x - x0];
-      fb.out = out_all.data() + o_out[x - x0];
-      if (!fb.grp->uniform) {
-        fb.sidx.resize(fb.nb * k);
-        fb.lidx.resize(fb.nb * e);
-      }
-    }
     tm.lap("alloc");
-    // (batch, block) pairs copied in on the pool
-    std::vector<std::pair<size_t, size_t>> work;
-    for (size_t x = x0; x < x1; ++x)
-      for (size_t bi = 0; bi < batches[x].nb; ++bi) work.emplace_back(x, bi);
     pool_.parallel_for(work.size(), [&](size_t t) {
-      FBatch& fb = batches[work[t].first];
-      const size_t bi = work[t].second;
-      Gathered& x = g[fb.grp->ids[fb.b0 + bi]];
+      const size_t x = work[t].first, bi = work[t].second;
+      const RebuildBatch& b = bs[x];
+      const size_t i = b.items[bi], Sb = items[i].S;
+      const uint8_t* src[MEMO_EC_MAX_K];
+      survivors(i, src);
       for (int s = 0; s < k; ++s) {
-        uint8_t* slot = fb.surv + (bi * k + s) * fb.S;
-        std::memcpy(slot, x.payload(s), x.h.shard_size);
-        std::memset(slot + x.h.shard_size, 0, fb.S - x.h.shard_size);
-        if (!fb.grp->uniform) fb.sidx[bi * k + s] = (uint8_t)x.shards[s].first;
+        uint8_t* slot = surv_all.data() + o_surv[x] + (bi * k + s) * b.S;
+        std::memcpy(slot, src[s], Sb);
+        std::memset(slot + Sb, 0, b.S - Sb);
       }
-      if (!fb.grp->uniform) std::copy(x.lost.begin(), x.lost.end(), fb.lidx.begin() + bi * fb.grp->e);
+      if (!b.uniform) {
+        std::copy(items[i].pat, items[i].pat + k, sidx[x].begin() + bi * k);
+        std::copy(items[i].pat + k, items[i].pat + k + b.e, lidx[x].begin() + bi * b.e);
+      }
     });
     tm.lap("copy_in");
+    if (staged) {
+      pool_.parallel_for(work.size(), [&](size_t t) { staged(bs[work[t].first].items[work[t].second]); });
+      tm.lap("free");
+    }
     std::vector<memo_ec_rebuild_segment> segs;
-    for (size_t x = x0; x < x1; ++x) {
-      const FBatch& fb = batches[x];
+    for (size_t x = 0; x < nx; ++x) {
       memo_ec_rebuild_segment sg{};
       sg.k = k;
       sg.m = m;
-      sg.S = fb.S;
-      sg.n = fb.nb;
-      sg.e = fb.grp->e;
-      sg.uniform = fb.grp->uniform ? 1 : 0;
-      sg.surv = fb.surv;
-      sg.out = fb.out;
-      sg.surv_idx = fb.grp->uniform ? fb.grp->pat.data() : fb.sidx.data();
-      sg.lost_idx = fb.grp->uniform ? fb.grp->pat.data() + k : fb.lidx.data();
+      sg.S = bs[x].S;
+      sg.n = bs[x].items.size();
+      sg.e = bs[x].e;
+      sg.uniform = bs[x].uniform ? 1 : 0;
+      sg.surv = surv_all.data() + o_surv[x];
+      sg.out = out_all.data() + o_out[x];
+      sg.surv_idx = bs[x].uniform ? bs[x].pat.data() : sidx[x].data();
+      sg.lost_idx = bs[x].uniform ? bs[x].pat.data() + k : lidx[x].data();
       segs.push_back(sg);
     }
-    codec_.rebuild_segments(segs, pin);
+    codec_.rebuild_segments(segs, surv_all.pinned() && out_all.pinned());
     tm.lap("rebuild");
-    for (size_t x = x0; x < x1; ++x) decoded_ += batches[x].nb;
     pool_.parallel_for(work.size(), [&](size_t t) {
-      FBatch& fb = batches[work[t].first];
+      const RebuildBatch& b = bs[work[t].first];
       const size_t bi = work[t].second;
-      finish(fb.grp->ids[fb.b0 + bi], fb.out + bi * fb.grp->e * fb.S, fb.S);
+      rebuilt(b.items[bi], segs[work[t].first].out + bi * b.e * b.S, b.S);
     });
-    tm.lap("assemble");
+    tm.lap(rebuilt_lap);
   }
-  for (size_t i = 0; i < n; ++i) res(addresses[i], std::move(blocks[i]), errs[i]);
+  return cuts.size() - 1;
 }
 
 void ErasureConsensus::_resign() { backend_->resign(); }
@@ -1914,15 +1932,7 @@ ErasureConsensus::RepairReport ErasureConsensus::repair_blocks(const std::vector
   std::lock_guard<std::mutex> rl(repair_mu_);
   RepairReport rep;
   rep.blocks_checked = blocks.size();
-  const int k = o_.k, m = o_.m, total = k + m;
-  struct Todo {
-    Address a;
-    Placement pl;
-    std::vector<int> lost;      // shards to rebuild
-    std::vector<uint8_t> sidx;  // the k validated survivors' indices
-    Buffer surv;                // their payloads, k x Sb, read in place from the silos
-    bool skip = false;
-  };
+  const int k = o_.k;
   // Chunks of blocks whose survivors are held in memory at once: up to
   // stage_bytes of shards (by the recorded block sizes), so that small blocks
   // still fill whole GPU batches per (size, e) group.
@@ -1941,67 +1951,11 @@ ErasureConsensus::RepairReport ErasureConsensus::repair_blocks(const std::vector
     if (cuts.back() != blocks.size()) cuts.push_back(blocks.size());
   }
   for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
-    const size_t c0 = cuts[ci], cn = cuts[ci + 1] - c0;
     PhaseTimer tm("repair_chunk");
-    std::vector<Todo> todo(cn);
-    // Scan: a shard is lost when its holder is gone (null, evicted, down
-    // with include_down), lacks it, or holds a copy that fails validation
-    // or belongs to another block or geometry; the first k valid shards
-    // found are the survivors.
-    std::shared_lock<std::shared_mutex> scan_lock(index_mu_);  // for the whole scan (see _fetch)
-    pool_.parallel_for(cn, [&](size_t t) {
-      Todo& x = todo[t];
-      x.a = blocks[c0 + t];
-      {
-        auto it = index_.find(x.a);
-        if (it == index_.end()) {
-          x.skip = true;  // removed meanwhile
-          return;
-        }
-        x.pl = it->second;
-      }
-      const ShardHeader ref = header_of(x.a, x.pl, 0);
-      const size_t Sb = ref.shard_size;
-      const ShardKeys keys(x.a);
-      x.surv.resize((size_t)k * Sb);
-      for (int i = 0; i < total; ++i) {
-        const Address& o = i < (int)x.pl.holder.size() ? x.pl.holder[i] : Address();
-        auto nd = o ? overlay_.node(o) : nullptr;
-        if (!nd || nd->evicted || (!nd->up && include_down)) {
-          x.lost.push_back(i);
-          continue;
-        }
-        if (!nd->up) continue;  // unreachable for now: neither lost nor usable
-        const Key key = keys(i);
-        if ((int)x.sidx.size() < k) {
-          // validated on the silo's view, the payload copied into its
-          // survivor slot (no copy of the whole shard)
-          bool ok = false;
-          auto take = [&](const uint8_t* w, size_t n) {
-            try {
-              const uint8_t* pay = nullptr;
-              const ShardHeader h = decode_shard_view(w, n, &pay);
-              if (h.index != i || !h.same_block(ref)) return;
-              if (Sb) std::memcpy(x.surv.data() + x.sidx.size() * Sb, pay, Sb);
-              ok = true;
-            } catch (ValidationFailed&) {
-            }
-          };
-          try {
-            nd->try_read(key, take);
-          } catch (Unavailable&) {
-            continue;
-          }
-          if (ok) x.sidx.push_back((uint8_t)i);
-          else x.lost.push_back(i);
-        } else if (!nd->has(key)) {
-          x.lost.push_back(i);
-        }
-      }
-    });
-    scan_lock.unlock();  // placement below takes the index exclusively
+    std::vector<Todo> todo = scan_for_repair(blocks, cuts[ci], cuts[ci + 1] - cuts[ci], include_down);
     tm.lap("scan");
     std::vector<Todo*> work;
+    std::vector<RebuildItem> items;
     for (auto& x : todo) {
       if (x.skip || x.lost.empty()) continue;
       if ((int)x.sidx.size() < k) {
@@ -2009,234 +1963,187 @@ ErasureConsensus::RepairReport ErasureConsensus::repair_blocks(const std::vector
         continue;
       }
       work.push_back(&x);
+      RebuildItem it{memo_ec_shard_size(x.pl.B, k), (int)x.lost.size(), {}};
+      std::copy(x.sidx.begin(), x.sidx.end(), it.pat);
+      std::copy(x.lost.begin(), x.lost.end(), it.pat + k);  // (int -> uint8_t)
+      items.push_back(it);
     }
-    struct Group {
-      int e;
-      bool uniform;
-      std::vector<uint8_t> pat;  // survivors (k) || lost (e), uniform groups
-      std::vector<Todo*> items;
+    // ONE codec call for the chunk's batches (no staging limit: the chunk was
+    // cut above, over blocks), each block placed as it comes back
+    const auto batches = plan_rebuild_batches(items, k, o_.batch_max, o_.uniform_min, o_.uniform_min_bytes);
+    auto survivors = [&](size_t i, const uint8_t** p) {
+      for (int s = 0; s < k; ++s) p[s] = work[i]->surv.data() + (size_t)s * items[i].S;
     };
-    std::map<std::pair<int, std::vector<uint8_t>>, std::vector<Todo*>> by_pat;
-    for (auto* x : work) {
-      std::vector<uint8_t> pat;
-      pat.assign(x->sidx.begin(), x->sidx.end());
-      for (int i : x->lost) pat.push_back((uint8_t)i);
-      by_pat[{size_bucket(memo_ec_shard_size(x->pl.B, k)), std::move(pat)}].push_back(x);
-    }
-    std::vector<Group> gs;
-    std::map<std::pair<int, size_t>, std::vector<Todo*>> rest;
-    for (auto& bp : by_pat) {
-      const int e = (int)(bp.first.second.size() - (size_t)k);
-      const size_t bytes = bp.second.size() * (size_t)k * ((size_t)64 << bp.first.first);
-      if ((int)bp.second.size() >= o_.uniform_min && bytes >= o_.uniform_min_bytes)
-        gs.push_back({e, true, bp.first.second, bp.second});
-      else
-        for (auto* x : bp.second) rest[{bp.first.first, (size_t)e}].push_back(x);
-    }
-    for (auto& r : rest) gs.push_back({(int)r.first.second, false, {}, r.second});
-    // Batches of blocks with the same (S bucket, e), or the same erasure
-    // pattern (the repair of one lost node: shared tables, encode speed),
-    // all rebuilt by ONE codec call per chunk (memo_ec_rebuild_segments, a
-    // segment per batch), then placed batch by batch.
-    struct RBatch {
-      const Group* grp;
-      size_t b0, n, S;
-      std::vector<uint8_t> sidx, lidx;
-      uint8_t* surv = nullptr;  // this batch's part of the chunk's two leases
-      uint8_t* out = nullptr;
-    };
-    std::vector<RBatch> rbs;
-    for (auto& grp : gs)
-      for (size_t b0 = 0; b0 < grp.items.size(); b0 += o_.batch_max) {
-        RBatch rb;
-        rb.grp = &grp;
-        rb.b0 = b0;
-        rb.n = std::min<size_t>(o_.batch_max, grp.items.size() - b0);
-        rb.S = 0;  // the batch's largest shard; smaller shards zero-padded
-        for (size_t bi = 0; bi < rb.n; ++bi) rb.S = std::max(rb.S, memo_ec_shard_size(grp.items[b0 + bi]->pl.B, k));
-        rb.sidx.resize(rb.n * k);
-        rb.lidx.resize(rb.n * grp.e);
-        rbs.push_back(std::move(rb));
-      }
-    // one survivor and one output lease for the chunk, carved per batch (as
-    // in the multi-fetch: no pinned allocation per batch)
-    size_t surv_bytes = 0, out_bytes = 0;
-    std::vector<size_t> o_surv(rbs.size()), o_out(rbs.size());
-    for (size_t x = 0; x < rbs.size(); ++x) {
-      o_surv[x] = surv_bytes;
-      o_out[x] = out_bytes;
-      surv_bytes += (rbs[x].n * k * rbs[x].S + 63) & ~(size_t)63;
-      out_bytes += (rbs[x].n * rbs[x].grp->e * rbs[x].S + 63) & ~(size_t)63;
-    }
-    PinnedArena::Lease surv_all, out_all;
-    if (!rbs.empty()) {
-      surv_all = arena_.lease(surv_bytes);
-      out_all = arena_.lease(out_bytes);
-    }
-    tm.lap("alloc");
-    const bool pin = rbs.empty() || (surv_all.pinned() && out_all.pinned());
-    for (size_t x = 0; x < rbs.size(); ++x) {
-      rbs[x].surv = surv_all.data() + o_surv[x];
-      rbs[x].out = out_all.data() + o_out[x];
-    }
-    std::vector<std::pair<size_t, size_t>> units;  // (batch, block)
-    for (size_t x = 0; x < rbs.size(); ++x)
-      for (size_t bi = 0; bi < rbs[x].n; ++bi) units.emplace_back(x, bi);
-    pool_.parallel_for(units.size(), [&](size_t t) {
-      RBatch& rb = rbs[units[t].first];
-      const size_t bi = units[t].second, S = rb.S;
-      const int e = rb.grp->e;
-      Todo& x = *rb.grp->items[rb.b0 + bi];
-      const size_t Sb = memo_ec_shard_size(x.pl.B, k);
-      for (int s = 0; s < k; ++s) {
-        uint8_t* slot = rb.surv + (bi * k + s) * S;
-        std::memcpy(slot, x.surv.data() + (size_t)s * Sb, Sb);
-        std::memset(slot + Sb, 0, S - Sb);
-        rb.sidx[bi * k + s] = x.sidx[s];
-      }
-      for (int r = 0; r < e; ++r) rb.lidx[bi * e + r] = (uint8_t)x.lost[r];
-    });
-    tm.lap("copy_in");
-    pool_.parallel_for(units.size(), [&](size_t t) {
-      Todo& x = *rbs[units[t].first].grp->items[rbs[units[t].first].b0 + units[t].second];
-      Buffer().swap(x.surv);
-    });
-    tm.lap("free");
-    if (!rbs.empty()) {
-      std::vector<memo_ec_rebuild_segment> segs;
-      for (auto& rb : rbs) {
-        memo_ec_rebuild_segment sg{};
-        sg.k = k;
-        sg.m = m;
-        sg.S = rb.S;
-        sg.n = rb.n;
-        sg.e = rb.grp->e;
-        sg.uniform = rb.grp->uniform ? 1 : 0;
-        sg.surv = rb.surv;
-        sg.out = rb.out;
-        sg.surv_idx = rb.grp->uniform ? rb.grp->pat.data() : rb.sidx.data();
-        sg.lost_idx = rb.grp->uniform ? rb.grp->pat.data() + k : rb.lidx.data();
-        segs.push_back(sg);
-      }
-      codec_.rebuild_segments(segs, pin);
-      ++rep.codec_calls;
-      tm.lap("rebuild");
-    }
-    // Place each rebuilt shard on a reachable node holding none of the
-    // block's other shards (Overlay::allocate order); the stale copy on a
-    // reachable old holder is dropped.  One pass over the chunk's blocks,
-    // then one index update for all of them (per batch, the fixed costs of
-    // the two steps outweighed the work at 4 KiB blocks).
-    std::vector<int> placed(units.size(), 0);
-    pool_.parallel_for(units.size(), [&](size_t t) {
-      const RBatch& rb = rbs[units[t].first];
-      const size_t bi = units[t].second, S = rb.S;
-      const int e = rb.grp->e;
-      Todo& x = *rb.grp->items[rb.b0 + bi];
-      // the block's other holders (at most k + m: a flat list)
-      std::vector<Address> taken;
-      taken.reserve(total);
-      for (int i = 0; i < total; ++i)
-        if (x.pl.holder[i] && std::find(x.lost.begin(), x.lost.end(), i) == x.lost.end())
-          taken.push_back(x.pl.holder[i]);
-      auto cand = overlay_.allocate(x.a, (int)overlay_.size());
-      const ShardKeys keys(x.a);
-      const ShardHeader hdr = header_of(x.a, x.pl, 0);
-      size_t ci = 0;
-      for (int r = 0; r < e; ++r) {
-        const int i = x.lost[r];
-        const Address old = x.pl.holder[i];
-        // framed once; each candidate's silo may keep a reference to it
-        auto wire = std::make_shared<Buffer>(encode_shard(hdr, rb.out + (bi * e + r) * S, i));
-        x.pl.holder[i] = Address();
-        while (ci < cand.size()) {
-          auto& nd = cand[ci++];
-          if (std::find(taken.begin(), taken.end(), nd->id) != taken.end()) continue;
-          try {
-            nd->store_shared(keys(i), std::shared_ptr<const uint8_t>(wire, wire->data()), wire->size());
-            x.pl.holder[i] = nd->id;
-            taken.push_back(nd->id);
-            ++placed[t];
-            break;
-          } catch (Error&) {  // unreachable or full: the next candidate
-          }
-        }
-        if (old && old != x.pl.holder[i]) {
-          auto on = overlay_.node(old);
-          if (on && on->up && !on->evicted) {
-            try {
-              on->remove(keys(i));
-            } catch (Error&) {
-            }
-          }
-        }
-      }
-    });
-    tm.lap("place");
-    // the chunk's new placements enter the index under one lock
-    // (the changes are built beforehand, on the pool: under the lock only
-    // the lookups and swaps)
-    std::vector<char> gone(units.size(), 0);
-    std::vector<NodeIndex::Change> ch(units.size());
-    pool_.parallel_for(units.size(), [&](size_t t) {
-      const RBatch& rb = rbs[units[t].first];
-      const Todo& x = *rb.grp->items[rb.b0 + units[t].second];
-      ch[t].block = x.a;
-      ch[t].new_h = x.pl.holder;
-    });
+    auto staged = [&](size_t i) { Buffer().swap(work[i]->surv); };
+    auto rebuilt = [&](size_t i, const uint8_t* shards, size_t stride) { place_rebuilt(*work[i], shards, stride); };
+    rep.codec_calls += stage_rebuilds(items, batches, kNoStageLimit, survivors, staged, rebuilt, "place", tm);
+    if (batches.empty())  // the timing line keeps its laps
+      for (const char* lap : {"alloc", "copy_in", "free", "place"}) tm.lap(lap);
+    std::vector<Todo*> done;  // in batch order
+    for (auto& b : batches)
+      for (size_t i : b.items) done.push_back(work[i]);
+    commit_repairs(done, rep, tm);
+  }
+  return rep;
+}
+
+std::vector<ErasureConsensus::Todo> ErasureConsensus::scan_for_repair(const std::vector<Address>& blocks,
+                                                                      size_t c0, size_t cn,
+                                                                      bool include_down) {
+  const int k = o_.k, total = k + o_.m;
+  std::vector<Todo> todo(cn);
+  std::shared_lock<std::shared_mutex> scan_lock(index_mu_);  // for the whole scan (see _fetch)
+  pool_.parallel_for(cn, [&](size_t t) {
+    Todo& x = todo[t];
+    x.a = blocks[c0 + t];
     {
-      std::unique_lock<std::shared_mutex> lk(index_mu_);
-      for (size_t t = 0; t < units.size(); ++t) {
-        const RBatch& rb = rbs[units[t].first];
-        Todo& x = *rb.grp->items[rb.b0 + units[t].second];
-        auto it = index_.find(x.a);
-        if (it == index_.end()) {
-          gone[t] = 1;
-          continue;
-        }
-        ch[t].old_h = std::move(it->second.holder);
-        it->second = std::move(x.pl);  // x.pl unused from here
+      auto it = index_.find(x.a);
+      if (it == index_.end()) {
+        x.skip = true;  // removed meanwhile
+        return;
       }
+      x.pl = it->second;
     }
-    tm.lap("swap");
-    for (size_t t = 0; t < units.size(); ++t)
-      if (gone[t]) ch[t].new_h.clear();  // no index change for a removed block
-    nodes_.update_many(ch, &pool_);
-    tm.lap("index");
-    for (size_t t = 0; t < units.size(); ++t) {
-      const RBatch& rb = rbs[units[t].first];
-      const int e = rb.grp->e;
-      Todo& x = *rb.grp->items[rb.b0 + units[t].second];
-      if (gone[t]) {  // removed while being repaired: drop the new shards
-        for (int i : x.lost)
-          if (x.pl.holder[i])
-            if (auto nd = overlay_.node(x.pl.holder[i])) {
-              try {
-                nd->remove(shard_key(x.a, i));
-              } catch (Error&) {
-              }
-            }
+    const ShardHeader ref = header_of(x.a, x.pl, 0);
+    const size_t Sb = ref.shard_size;
+    const ShardKeys keys(x.a);
+    x.surv.resize((size_t)k * Sb);
+    for (int i = 0; i < total; ++i) {
+      const Address& o = i < (int)x.pl.holder.size() ? x.pl.holder[i] : Address();
+      auto nd = o ? overlay_.node(o) : nullptr;
+      if (!nd || nd->evicted || (!nd->up && include_down)) {
+        x.lost.push_back(i);
         continue;
       }
-      ++rep.blocks_repaired;
-      rep.shards_rebuilt += (size_t)placed[t];
-      rep.shards_unplaced += (size_t)e - (size_t)placed[t];
-      ++repaired_;
-      if (rebalanced_ && placed[t]) rebalanced_(x.a);  // moved onto new owners
-      if (placed[t] < e && under_placed_) {
-        // no reachable node could take the rest (Paxos.cc:1120-1126)
-        int held = 0;
-        {
-          std::shared_lock<std::shared_mutex> lk(index_mu_);
-          auto it = index_.find(x.a);
-          if (it != index_.end())
-            for (auto& h : it->second.holder) held += h ? 1 : 0;
+      if (!nd->up) continue;  // unreachable for now: neither lost nor usable
+      const Key key = keys(i);
+      if ((int)x.sidx.size() < k) {
+        // validated on the silo's view, the payload copied into its
+        // survivor slot (no copy of the whole shard)
+        bool ok = false;
+        auto take = [&](const uint8_t* w, size_t n) {
+          try {
+            const uint8_t* pay = nullptr;
+            const ShardHeader h = decode_shard_view(w, n, &pay);
+            if (h.index != i || !h.same_block(ref)) return;
+            if (Sb) std::memcpy(x.surv.data() + x.sidx.size() * Sb, pay, Sb);
+            ok = true;
+          } catch (ValidationFailed&) {
+          }
+        };
+        try {
+          nd->try_read(key, take);
+        } catch (Unavailable&) {
+          continue;
         }
-        under_placed_(x.a, held);
+        if (ok) x.sidx.push_back((uint8_t)i);
+        else x.lost.push_back(i);
+      } else if (!nd->has(key)) {
+        x.lost.push_back(i);
+      }
+    }
+  });
+  return todo;
+}
+
+void ErasureConsensus::place_rebuilt(Todo& x, const uint8_t* rebuilt, size_t stride) {
+  const int total = o_.k + o_.m, e = (int)x.lost.size();
+  // the block's other holders (at most k + m: a flat list)
+  std::vector<Address> taken;
+  taken.reserve(total);
+  for (int i = 0; i < total; ++i)
+    if (x.pl.holder[i] && std::find(x.lost.begin(), x.lost.end(), i) == x.lost.end())
+      taken.push_back(x.pl.holder[i]);
+  auto cand = overlay_.allocate(x.a, (int)overlay_.size());
+  const ShardKeys keys(x.a);
+  const ShardHeader hdr = header_of(x.a, x.pl, 0);
+  size_t ci = 0;
+  for (int r = 0; r < e; ++r) {
+    const int i = x.lost[r];
+    const Address old = x.pl.holder[i];
+    // framed once; each candidate's silo may keep a reference to it
+    auto wire = std::make_shared<Buffer>(encode_shard(hdr, rebuilt + r * stride, i));
+    x.pl.holder[i] = Address();
+    while (ci < cand.size()) {
+      auto& nd = cand[ci++];
+      if (std::find(taken.begin(), taken.end(), nd->id) != taken.end()) continue;
+      try {
+        nd->store_shared(keys(i), std::shared_ptr<const uint8_t>(wire, wire->data()), wire->size());
+        x.pl.holder[i] = nd->id;
+        taken.push_back(nd->id);
+        ++x.placed;
+        break;
+      } catch (Error&) {  // unreachable or full: the next candidate
+      }
+    }
+    if (old && old != x.pl.holder[i]) {
+      auto on = overlay_.node(old);
+      if (on && on->up && !on->evicted) {
+        try {
+          on->remove(keys(i));
+        } catch (Error&) {
+        }
       }
     }
   }
-  return rep;
+}
+
+void ErasureConsensus::commit_repairs(const std::vector<Todo*>& done, RepairReport& rep, PhaseTimer& tm) {
+  std::vector<char> gone(done.size(), 0);
+  std::vector<NodeIndex::Change> ch(done.size());
+  pool_.parallel_for(done.size(), [&](size_t t) {
+    ch[t].block = done[t]->a;
+    ch[t].new_h = done[t]->pl.holder;
+  });
+  {
+    std::unique_lock<std::shared_mutex> lk(index_mu_);
+    for (size_t t = 0; t < done.size(); ++t) {
+      Todo& x = *done[t];
+      auto it = index_.find(x.a);
+      if (it == index_.end()) {
+        gone[t] = 1;
+        continue;
+      }
+      ch[t].old_h = std::move(it->second.holder);
+      it->second = std::move(x.pl);  // x.pl unused from here
+    }
+  }
+  tm.lap("swap");
+  for (size_t t = 0; t < done.size(); ++t)
+    if (gone[t]) ch[t].new_h.clear();  // no index change for a removed block
+  nodes_.update_many(ch, &pool_);
+  tm.lap("index");
+  for (size_t t = 0; t < done.size(); ++t) {
+    Todo& x = *done[t];
+    const int e = (int)x.lost.size();
+    if (gone[t]) {  // removed while being repaired: drop the new shards
+      for (int i : x.lost)
+        if (x.pl.holder[i])
+          if (auto nd = overlay_.node(x.pl.holder[i])) {
+            try {
+              nd->remove(shard_key(x.a, i));
+            } catch (Error&) {
+            }
+          }
+      continue;
+    }
+    ++rep.blocks_repaired;
+    rep.shards_rebuilt += (size_t)x.placed;
+    rep.shards_unplaced += (size_t)e - (size_t)x.placed;
+    ++repaired_;
+    if (rebalanced_ && x.placed) rebalanced_(x.a);  // moved onto new owners
+    if (x.placed < e && under_placed_) {
+      // no reachable node could take the rest (Paxos.cc:1120-1126)
+      int held = 0;
+      {
+        std::shared_lock<std::shared_mutex> lk(index_mu_);
+        auto it = index_.find(x.a);
+        if (it != index_.end())
+          for (auto& h : it->second.holder) held += h ? 1 : 0;
+      }
+      under_placed_(x.a, held);
+    }
+  }
 }
 
 ErasureConsensus::RepairReport ErasureConsensus::repair(bool include_down) {
@@ -2339,8 +2246,6 @@ ErasureConsensus::ScrubReport ErasureConsensus::scrub(const std::vector<Address>
       } catch (Error&) {
         return;  // skipped
       }
-      std::sort(g.have.begin(), g.have.end(),
-                [](const auto& x, const auto& y) { return x.first < y.first; });
       g.complete = (int)g.have.size() == total && g.h.shard_size == items[i0 + t].S;
     });
     // groups of one shard size: one verify call each
@@ -2382,15 +2287,10 @@ ErasureConsensus::ScrubReport ErasureConsensus::scrub(const std::vector<Address>
           Buffer block(data.data() + x * k * S, data.data() + (x + 1) * k * S);  // k x S
           if (v.shard < k) {
             // rebuild data shard j from the k lowest other shards
-            std::vector<uint8_t> sidx;
-            Buffer surv((size_t)k * S), out(S);
-            for (int i = 0; i < total && (int)sidx.size() < k; ++i) {
-              if (i == v.shard) continue;
-              std::memcpy(surv.data() + sidx.size() * S, g.have[i].second.data() + ShardHeader::kSize, S);
-              sidx.push_back((uint8_t)i);
-            }
-            const uint8_t lost = (uint8_t)v.shard;
-            codec_.rebuild(k, m, S, 1, sidx.data(), surv.data(), &lost, 1, out.data());
+            std::vector<ShardRef> picks;
+            for (int i = 0; i < total && (int)picks.size() < k; ++i)
+              if (i != v.shard) picks.emplace_back(i, g.have[i].second.data() + ShardHeader::kSize);
+            const Buffer out = rebuild_one(S, picks, {(uint8_t)v.shard});
             std::memcpy(block.data() + (size_t)v.shard * S, out.data(), S);
           }
           // (a parity shard: the data shards stand as they are, and the

@@ -34,6 +34,8 @@
 
 namespace memo_host {
 
+struct PhaseTimer;  // erasure_consensus.cc: the MEMO_EC_PLUGIN_TIMING laps
+
 // --------------------------------------------------------------- codec
 // libmemo_ec contexts for host-memory calls.  A ctx serves one thread at a
 // time (memo_ec.h); a small pool per GPU lets concurrent fetch threads
@@ -174,6 +176,37 @@ constexpr size_t kFrameRunBytes = (size_t)256 << 10;
 // Default shard bytes one store_many, fetch or repair chunk stages (pinned)
 // and hands to one codec call at most (ErasureOptions::stage_bytes).
 constexpr size_t kStageBytes = (size_t)512 << 20;
+
+// ------------------------------------------------------- rebuild planning
+// How the multi-fetch and the repair batch their degraded blocks for one
+// memo_ec_rebuild_segments call: pure functions of the blocks' shard sizes
+// and erasure patterns (no codec, arena, pool or index).
+struct RebuildItem {
+  size_t S;  // the block's shard size
+  int e;     // shards it lost
+  // its k survivors' indices, then the e lost ones (in place: thousands of
+  // items per fetch, no allocation each)
+  uint8_t pat[MEMO_EC_MAX_K + MEMO_EC_MAX_M];
+};
+struct RebuildBatch {
+  int e;
+  bool uniform;               // every member has the pattern `pat`
+  size_t S;                   // the largest member's; smaller shards are zero-padded
+  std::vector<uint8_t> pat;   // uniform batches: survivors (k) || lost (e)
+  std::vector<size_t> items;  // members, as positions in the planner's input
+};
+// Items by (shard-size bucket, pattern); a pattern that at least uniform_min
+// items and uniform_min_bytes of survivors (at the bucket's largest size)
+// share makes a uniform group, the others pool by (bucket, e) in pattern
+// order; uniform groups first, every group cut each batch_max members.
+std::vector<RebuildBatch> plan_rebuild_batches(const std::vector<RebuildItem>& items, int k,
+                                               int batch_max, int uniform_min,
+                                               size_t uniform_min_bytes);
+// Chunks of batches staged at once, [cuts[c], cuts[c + 1]): cut before a
+// batch that would take a chunk's survivors (n x k x S) past `limit` bytes;
+// no chunk for no batches.
+constexpr size_t kNoStageLimit = ~(size_t)0;
+std::vector<size_t> cut_rebuild_chunks(const std::vector<RebuildBatch>& batches, int k, size_t limit);
 
 // ---------------------------------------------------------- shard format
 // On-wire / on-silo shard: a 128-byte header + S payload bytes.  The header
@@ -538,6 +571,10 @@ class ErasureConsensus : public StackedConsensus {
   // subsets matches and a wider gather is left to try
   std::unique_ptr<Block> recover_from(const Address& a, int want, bool parallel,
                                       size_t* rewritten = nullptr);
+  // One block's `lost` shards (e x S) from k of its shards (index, S payload
+  // bytes each), by a per-block codec call (single fetch, recovery, scrub).
+  using ShardRef = std::pair<int, const uint8_t*>;
+  Buffer rebuild_one(size_t S, const std::vector<ShardRef>& from, const std::vector<uint8_t>& lost);
   // The shards in `have` that disagree with the verified k x S block
   // rewritten on the holders that served them (recover_from and scrub).
   size_t rewrite_disagreeing(const Address& a, const ShardHeader& h, const Buffer& padded_block,
@@ -548,8 +585,55 @@ class ErasureConsensus : public StackedConsensus {
   // caller updates after releasing the lock
   std::vector<Address> swap_placement_locked(const Address& a, Placement pl);
   std::vector<Address> erase_placement_locked(const Address& a);
-  // The repair engine: rebuild and re-place the lost shards of `blocks`.
+  // The staged rebuild of the multi-fetch and the repair: `batches` (planned
+  // over `items`) in chunks of at most `limit` survivor bytes, each chunk one
+  // survivor and one output lease carved per batch (a lease per batch took a
+  // pinned allocation each, ~2 ms apiece: 240 ms for 16,384 4 KiB blocks) and
+  // ONE codec call.  Per item, on the pool: survivors(i, p) gives its k
+  // payloads (items[i].S bytes each); staged(i), if any, runs once they are
+  // copied in, before the codec call; rebuilt(i, shards, stride) gets lost
+  // shard r at shards + r * stride (that pass's timing lap: rebuilt_lap).
+  // Returns the codec calls made.
+  using Survivors = std::function<void(size_t, const uint8_t**)>;
+  using Rebuilt = std::function<void(size_t, const uint8_t*, size_t)>;
+  size_t stage_rebuilds(const std::vector<RebuildItem>& items, const std::vector<RebuildBatch>& batches,
+                        size_t limit, const Survivors& survivors, const std::function<void(size_t)>& staged,
+                        const Rebuilt& rebuilt, const char* rebuilt_lap, PhaseTimer& tm);
+  // One shard-size bucket of blocks encoded: their shards zero-padded into
+  // S-byte slots (S the largest) of two leases, copied in on the pool or
+  // serially, then one encode call.
+  struct Encoded {
+    PinnedArena::Lease data, parity;  // n x k x S, n x m x S
+    size_t S;
+  };
+  Encoded encode_bucket(const std::vector<const Block*>& bs, bool on_pool, PhaseTimer* tm);
+  // The repair engine: rebuild and re-place the lost shards of `blocks`, a
+  // chunk at a time: scan, plan and stage (placing each block as it comes
+  // back), commit.
   RepairReport repair_blocks(const std::vector<Address>& blocks, bool include_down);
+  struct Todo {
+    Address a;
+    Placement pl;
+    std::vector<int> lost;      // shards to rebuild
+    std::vector<uint8_t> sidx;  // the k validated survivors' indices
+    Buffer surv;                // their payloads, k x Sb, read in place from the silos
+    bool skip = false;
+    int placed = 0;             // rebuilt shards that found a new holder
+  };
+  // blocks [c0, c0 + cn): a shard is lost when its holder is gone (null,
+  // evicted, down with include_down), lacks it, or holds a copy that fails
+  // validation or belongs to another block or geometry; the first k valid
+  // shards found are the survivors
+  std::vector<Todo> scan_for_repair(const std::vector<Address>& blocks, size_t c0, size_t cn,
+                                    bool include_down);
+  // each rebuilt shard onto a reachable node holding none of the block's
+  // other shards (Overlay::allocate order); the stale copy on a reachable
+  // old holder is dropped
+  void place_rebuilt(Todo& x, const uint8_t* rebuilt, size_t stride);
+  // the chunk's new placements into the index under one lock (the changes
+  // built beforehand, on the pool), then the node index, the counters and
+  // the callbacks, block by block
+  void commit_repairs(const std::vector<Todo*>& done, RepairReport& rep, PhaseTimer& tm);
   void settle_removes(const Address& node, bool evicted);
   // membership: overlay events -> the membership thread
   void membership_loop();

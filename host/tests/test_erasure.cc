@@ -616,6 +616,58 @@ TEST(pinned_arena_drops_outsized_buffers, false) {
   CHECK(a.kept_bytes() == (size_t)1 << 20 && a.leases() == 3);
 }
 
+// The rebuild planner (plan_rebuild_batches) on ten items of k = 4: five
+// share one pattern, sizes 192 and 256 share a bucket, one item lost two.
+namespace {
+std::vector<RebuildItem> plan_items() {
+  std::vector<RebuildItem> it;
+  // shard size, e, k survivors then e lost
+  it.push_back({128, 1, {0, 1, 2, 4, 3}});
+  for (int i = 1; i <= 5; ++i) it.push_back({128, 1, {1, 2, 3, 4, 0}});
+  it.push_back({128, 1, {0, 1, 2, 5, 3}});
+  it.push_back({256, 1, {1, 2, 3, 4, 0}});
+  it.push_back({192, 1, {1, 2, 3, 4, 0}});
+  it.push_back({128, 2, {2, 3, 4, 5, 0, 1}});
+  return it;
+}
+bool batch_is(const RebuildBatch& b, bool uniform, int e, size_t S, std::vector<size_t> members) {
+  const std::vector<uint8_t> shared{1, 2, 3, 4, 0};
+  return b.uniform == uniform && b.e == e && b.S == S && b.items == members &&
+         (!uniform || b.pat == shared);
+}
+}  // namespace
+
+TEST(rebuild_plan_uniform_groups_first, false) {
+  const auto b = plan_rebuild_batches(plan_items(), 4, 4, 4, 0);
+  CHECK(b.size() == 5);
+  if (b.size() != 5) return;
+  CHECK(batch_is(b[0], true, 1, 128, {1, 2, 3, 4}));
+  CHECK(batch_is(b[1], true, 1, 128, {5}));
+  CHECK(batch_is(b[2], false, 1, 128, {0, 6}));
+  CHECK(batch_is(b[3], false, 2, 128, {9}));
+  CHECK(batch_is(b[4], false, 1, 256, {7, 8}));  // one bucket, the larger S
+  // the multi-fetch's chunks: cut before the batch that passes the limit
+  CHECK((cut_rebuild_chunks(b, 4, 2560) == std::vector<size_t>{0, 2, 4, 5}));
+  CHECK((cut_rebuild_chunks(b, 4, kNoStageLimit) == std::vector<size_t>{0, 5}));
+}
+
+TEST(rebuild_plan_below_uniform_bytes_pools_by_erasures, false) {
+  const auto b = plan_rebuild_batches(plan_items(), 4, 4, 4, ErasureOptions().uniform_min_bytes);
+  CHECK(b.size() == 4);
+  if (b.size() != 4) return;
+  // patterns in order, then input order, cut every batch_max
+  CHECK(batch_is(b[0], false, 1, 128, {0, 6, 1, 2}));
+  CHECK(batch_is(b[1], false, 1, 128, {3, 4, 5}));
+  CHECK(batch_is(b[2], false, 2, 128, {9}));
+  CHECK(batch_is(b[3], false, 1, 256, {7, 8}));
+}
+
+TEST(rebuild_plan_of_nothing_is_empty, false) {
+  const auto b = plan_rebuild_batches({}, 4, 4, 4, 0);
+  CHECK(b.empty());
+  CHECK((cut_rebuild_chunks(b, 4, 2560) == std::vector<size_t>{0}));  // no chunk: no lease, no call
+}
+
 // -------------------------------------------------------------- GPU tests
 // tests/doughnut.cc:320-335 (CHB): insert -> fetch equal -> remove.
 TEST(CHB, true) {
