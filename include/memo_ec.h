@@ -34,6 +34,21 @@
  *            (the survivors' bytes, in surv_idx order), lost_idx n x e,
  *            out n x e x S (the rebuilt shards, in lost_idx order).
  *
+ * Alignment: a shard buffer (data, parity, surv, out, and the same fields of
+ * a segment) in MEMO_EC_DEVICE or MEMO_EC_HOST_PINNED memory must be 16-byte
+ * aligned, and a verdict array 4-byte aligned in any memory; a call that is
+ * handed anything else returns MEMO_EC_EINVAL before anything is enqueued.
+ * The kernels reach those buffers as the caller passed them, with 16-byte
+ * vector loads and stores and 4-byte atomics on the verdict words; what this
+ * part does with such an access at an odd address has not been measured, and
+ * shared hardware is no place to find out.  S is a multiple of 64, so every
+ * block and shard of an aligned buffer is aligned.  Pageable MEMO_EC_HOST
+ * shard buffers may sit at any byte address (the library copies them), as
+ * may every index array, the rows of memo_ec_decode_rows and the messages
+ * and prefixes of memo_ec_sha256_batch (byte accesses where the address
+ * asks for them).  The device-only calls state theirs where they are
+ * declared.
+ *
  * Threading (mirrors elle::reactor::background, elle/src/elle/reactor/
  * scheduler.cc:562-602, which runs CPU work on <= 16 pool threads): a ctx is
  * used by one thread at a time; distinct ctxs are independent, so each pool
@@ -237,8 +252,8 @@ int memo_ec_rebuild_batch(memo_ec_ctx *ctx, int k, int m, size_t S, size_t n,
  * replaced by XOR.  mode MEMO_EC_PROBE_COPY: out shard i of block b = XOR
  * of its kin input shards, every byte XOR i; MEMO_EC_PROBE_READ: the loads
  * alone (out unspecified); MEMO_EC_PROBE_WRITE: the stores alone (out
- * unspecified).  Device pointers only (in n x kin x S, out n x r x S);
- * asynchronous on the ctx stream.  The read and write launches' times
+ * unspecified).  Device pointers only (in n x kin x S, out n x r x S), both
+ * 16-byte aligned (MEMO_EC_EINVAL otherwise); asynchronous on the ctx stream.  The read and write launches' times
  * added give the "achievable" rate of the codec's roofline: this mix of
  * read and write streams without the cost of interleaving them (bench.py:
  * roofline.achievable, frac_of_achievable). */
@@ -278,7 +293,8 @@ int memo_ec_rebuild_uniform(memo_ec_ctx *ctx, int k, int m, size_t S, size_t n,
  * coefficients of lost_idx[b][r] over the survivors in surv_idx[b] order,
  * i.e. C[lost] * inv(C[surv]) -- computed in closed form (one lane per block,
  * no matrix inversion), as memo_ec_rebuild_batch does before its
- * multiply-accumulate.  Device pointers only; asynchronous on the ctx
+ * multiply-accumulate.  Device pointers only, at any byte alignment (rows
+ * off a 4-byte boundary are stored byte-wise); asynchronous on the ctx
  * stream; invalid survivor sets give zero rows and MEMO_EC_ESINGULAR at
  * memo_ec_synchronize. */
 int memo_ec_decode_rows(memo_ec_ctx *ctx, int k, int m, size_t n,
@@ -287,8 +303,9 @@ int memo_ec_decode_rows(memo_ec_ctx *ctx, int k, int m, size_t n,
 
 /* Batched encode of up to MEMO_EC_MAX_SEGMENTS device-resident segments
  * with different (k, m, S): segments of one shard-chunk class (same
- * specialised k) share one launch, classes run back to back.  Asynchronous
- * on the ctx stream. */
+ * specialised k) share one launch, classes run back to back.  Every
+ * segment's data and parity are 16-byte aligned (MEMO_EC_EINVAL otherwise,
+ * before anything is enqueued).  Asynchronous on the ctx stream. */
 int memo_ec_encode_segments(memo_ec_ctx *ctx, int nseg,
                             const memo_ec_segment *segs);
 
@@ -317,7 +334,9 @@ int memo_ec_rebuild_segments(memo_ec_ctx *ctx, int nseg,
  * (src/memo/model/doughnut/CHB.cc:264-289) and of CHB::_validate
  * (CHB.cc:79-99) for a whole batch; the caller sets address byte 31 to the
  * immutable flag (model/Address.hh: flag_byte).  Device pointers only;
- * asynchronous on the ctx stream. */
+ * prefix and msg at any byte alignment, digest 4-byte and msg_len 8-byte
+ * aligned (word stores and loads; MEMO_EC_EINVAL otherwise); asynchronous on
+ * the ctx stream. */
 int memo_ec_sha256_batch(memo_ec_ctx *ctx, size_t n, const uint8_t *prefix,
                          size_t prefix_len, size_t prefix_stride,
                          const uint8_t *msg, size_t msg_stride,
@@ -325,7 +344,9 @@ int memo_ec_sha256_batch(memo_ec_ctx *ctx, size_t n, const uint8_t *prefix,
                          uint8_t *digest);
 
 /* Synthetic workload helpers (device memory; asynchronous on the ctx
- * stream).  Bytes and erasure patterns follow DESIGN.md section 6. */
+ * stream).  Bytes and erasure patterns follow DESIGN.md section 6.  The
+ * shard buffers (fill's out; gather's data, parity and out) are 16-byte
+ * aligned, MEMO_EC_EINVAL otherwise; gather's idx may sit anywhere. */
 int memo_ec_fill_blocks(memo_ec_ctx *ctx, uint64_t seed, uint64_t first_block,
                         size_t n, size_t B, int k, size_t S, uint8_t *out);
 int memo_ec_erasures(uint64_t seed, uint64_t first_block, size_t n, int k,

@@ -255,6 +255,13 @@ int check_km(int k, int m) {
   return MEMO_EC_OK;
 }
 
+// The pointer contract of include/memo_ec.h, checked before anything is
+// enqueued.  The kernels reach MEMO_EC_DEVICE and MEMO_EC_HOST_PINNED shard
+// buffers as the caller passed them, with 16-byte vector loads and stores;
+// pageable buffers only ever meet memcpy.
+bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+bool shard_misaligned(int where, const void* p) { return where != MEMO_EC_HOST && misaligned(p, 16); }
+
 // One segment of a MAC launch plus the compile-time bounds it needs.
 struct Plan {
   MacSeg seg{};
@@ -1020,7 +1027,7 @@ size_t rows_scratch(const Pieces& ps) {
 // pieces[i] describes segment i whole (pointers as the caller gave them).
 // Shared patterns are decoded (and their tables cached) here, before
 // anything is enqueued.
-int plan_rebuild_segments(memo_ec_ctx* c, int nseg, const memo_ec_rebuild_segment* segs,
+int plan_rebuild_segments(memo_ec_ctx* c, int nseg, const memo_ec_rebuild_segment* segs, int where,
                           std::vector<RPiece>& pieces) {
   pieces.clear();
   for (int i = 0; i < nseg; ++i) {
@@ -1029,6 +1036,7 @@ int plan_rebuild_segments(memo_ec_ctx* c, int nseg, const memo_ec_rebuild_segmen
     if (s.e < 0 || s.e > s.m) return MEMO_EC_EINVAL;
     if (s.e == 0 || s.n == 0) continue;
     if (s.S == 0 || s.S % 64 || !s.surv_idx || !s.surv || !s.lost_idx || !s.out) return MEMO_EC_EINVAL;
+    if (shard_misaligned(where, s.surv) || shard_misaligned(where, s.out)) return MEMO_EC_EINVAL;
     if (s.S >= kMaxShard || too_big(s.n, (size_t)(s.k + s.e) * s.S + s.k + s.e)) return MEMO_EC_ERANGE;
     RPiece p;
     p.seg = i;
@@ -1263,7 +1271,7 @@ int take_deferred(memo_ec_ctx* ctx) {
 int rebuild_segments_impl(memo_ec_ctx* c, int nseg, const memo_ec_rebuild_segment* segs, int where) {
   DeviceGuard g(c->device);
   std::vector<RPiece> ps;
-  if (int rc = plan_rebuild_segments(c, nseg, segs, ps)) return rc;
+  if (int rc = plan_rebuild_segments(c, nseg, segs, where, ps)) return rc;
   if (ps.empty()) return MEMO_EC_OK;
   // Per-block pieces use the ctx's scratch (decode rows, table images) and
   // its ordering event; a call of shared patterns alone touches neither.
@@ -1643,6 +1651,7 @@ int memo_ec_encode_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const
   if (int rc = check_km(k, m)) return rc;
   if (m == 0 || n == 0) return MEMO_EC_OK;
   if (S == 0 || S % 64 != 0 || !data || !parity) return MEMO_EC_EINVAL;
+  if (shard_misaligned(where, data) || shard_misaligned(where, parity)) return MEMO_EC_EINVAL;
   if (S >= kMaxShard || too_big(n, (size_t)(k + m) * S)) return MEMO_EC_ERANGE;
   DeviceGuard g(c->device);
   if (where == MEMO_EC_DEVICE) return encode_device(c, k, m, S, n, data, parity, c->stream);
@@ -1661,6 +1670,8 @@ int memo_ec_verify_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const
   if (int rc = check_km(k, m)) return rc;
   if (m == 0 || n == 0) return MEMO_EC_OK;
   if (S == 0 || S % 64 != 0 || !data || !parity || !verdict) return MEMO_EC_EINVAL;
+  if (shard_misaligned(where, data) || shard_misaligned(where, parity) || misaligned(verdict, 4))
+    return MEMO_EC_EINVAL;
   if (S >= kMaxShard || too_big(n, (size_t)(k + m) * S)) return MEMO_EC_ERANGE;
   DeviceGuard g(c->device);
   if (where == MEMO_EC_DEVICE) return verify_device(c, k, m, S, n, data, parity, verdict, c->stream);
@@ -1674,6 +1685,7 @@ int memo_ec_stream_probe(memo_ec_ctx* c, int kin, int r, size_t S, size_t n, con
   if (int rc = check_km(kin, r)) return rc;
   if (r == 0 || n == 0) return MEMO_EC_OK;
   if (S == 0 || S % 64 != 0 || !in || !out) return MEMO_EC_EINVAL;
+  if (misaligned(in, 16) || misaligned(out, 16)) return MEMO_EC_EINVAL;
   if (S >= kMaxShard || too_big(n, (size_t)(kin + r) * S)) return MEMO_EC_ERANGE;
   DeviceGuard g(c->device);
   // the encode's geometry for (k, m) = (kin, r), launched as the probe
@@ -1776,6 +1788,7 @@ int memo_ec_encode_segments(memo_ec_ctx* c, int nseg, const memo_ec_segment* seg
     if (segs[i].m == 0 || segs[i].n == 0) continue;
     if (segs[i].S == 0 || segs[i].S % 64 || !segs[i].data || !segs[i].parity)
       return MEMO_EC_EINVAL;
+    if (misaligned(segs[i].data, 16) || misaligned(segs[i].parity, 16)) return MEMO_EC_EINVAL;
     if (segs[i].S >= kMaxShard) return MEMO_EC_ERANGE;
     if (segs[i].n > max_blocks_per_launch(c, segs[i].S)) return MEMO_EC_ERANGE;
     if (too_big(segs[i].n, (size_t)(segs[i].k + segs[i].m) * segs[i].S)) return MEMO_EC_ERANGE;
@@ -1821,6 +1834,7 @@ int memo_ec_sha256_batch(memo_ec_ctx* c, size_t n, const uint8_t* prefix, size_t
                          const uint64_t* msg_len, size_t uniform_len, uint8_t* digest) {
   if (!c || (n && (!digest || !msg || (prefix_len && !prefix)))) return MEMO_EC_EINVAL;
   if (n == 0) return MEMO_EC_OK;
+  if (misaligned(digest, 4) || misaligned(msg_len, 8)) return MEMO_EC_EINVAL;  // word stores / loads
   if (n > 0x7fffffffull * 256) return MEMO_EC_ERANGE;
   DeviceGuard g(c->device);
   Sha256Args a{prefix, msg, msg_len, digest, n, prefix_len, prefix_stride, msg_stride, uniform_len};
@@ -1830,6 +1844,7 @@ int memo_ec_sha256_batch(memo_ec_ctx* c, size_t n, const uint8_t* prefix, size_t
 int memo_ec_fill_blocks(memo_ec_ctx* c, uint64_t seed, uint64_t first_block, size_t n, size_t B,
                         int k, size_t S, uint8_t* out) {
   if (!c || k < 1 || S % 16 || (size_t)k * S < B || (n && !out)) return MEMO_EC_EINVAL;
+  if (misaligned(out, 16)) return MEMO_EC_EINVAL;
   if (S >= kMaxShard || too_big(n, (size_t)k * S)) return MEMO_EC_ERANGE;
   DeviceGuard g(c->device);
   FillArgs a{out, seed, first_block, n, B, (uint64_t)k * S};
@@ -1839,6 +1854,8 @@ int memo_ec_fill_blocks(memo_ec_ctx* c, uint64_t seed, uint64_t first_block, siz
 int memo_ec_gather_shards(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const uint8_t* data,
                           const uint8_t* parity, const uint8_t* idx, int cnt, uint8_t* out) {
   if (!c || check_km(k, m) || S % 16 || cnt < 0 || (n && cnt && (!data || !idx || !out)))
+    return MEMO_EC_EINVAL;
+  if (n && cnt && (misaligned(data, 16) || misaligned(parity, 16) || misaligned(out, 16)))
     return MEMO_EC_EINVAL;
   if (S >= kMaxShard || too_big(n, (size_t)cnt * S + cnt)) return MEMO_EC_ERANGE;
   DeviceGuard g(c->device);
