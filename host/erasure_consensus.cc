@@ -224,6 +224,69 @@ void Codec::verify(int k, int m, size_t S, size_t n, const uint8_t* data, const 
   ++verify_calls_;
 }
 
+std::vector<size_t> cut_ragged_ranges(const size_t* sizes, size_t n, size_t parts) {
+  std::vector<size_t> cuts{0};
+  size_t total = 0;
+  for (size_t b = 0; b < n; ++b) total += sizes[b];
+  size_t acc = 0;
+  for (size_t b = 0; b < n && cuts.size() < parts; ++b) {
+    acc += sizes[b];
+    // cut behind block b once the bytes so far reach the next part's share
+    if (b + 1 < n && acc * parts >= total * cuts.size()) cuts.push_back(b + 1);
+  }
+  if (cuts.back() != n) cuts.push_back(n);
+  return cuts;
+}
+
+void Codec::split_ragged(size_t n, const size_t* sizes,
+                         const std::function<int(size_t, size_t, size_t, size_t)>& fn,
+                         const char* what) {
+  const size_t D = dev_.size();
+  if (D == 1 || n < 2 * D) {
+    const size_t d = D == 1 ? 0 : rr_++ % D;
+    check(fn(d, 0, n, 0), what);
+    return;
+  }
+  const std::vector<size_t> cuts = cut_ragged_ranges(sizes, n, D);
+  const size_t R = cuts.size() - 1;
+  std::vector<int> rc(R, MEMO_EC_OK);
+  std::vector<std::thread> ts;
+  size_t off = 0;
+  for (size_t d = 0; d < R; ++d) {
+    const size_t b0 = cuts[d], cnt = cuts[d + 1] - b0, o = off;
+    ts.emplace_back([&, d, b0, cnt, o] { rc[d] = fn(d, b0, cnt, o); });
+    for (size_t b = b0; b < b0 + cnt; ++b) off += sizes[b];
+  }
+  for (auto& t : ts) t.join();
+  for (int r : rc) check(r, what);
+}
+
+void Codec::encode_ragged(int k, int m, size_t n, const size_t* sizes, const uint8_t* data,
+                          uint8_t* parity, bool pinned) {
+  split_ragged(n, sizes, [&](size_t d, size_t b0, size_t cnt, size_t off) {
+    auto* c = acquire(d);
+    const int rc = memo_ec_encode_ragged(c, k, m, cnt, sizes + b0, data + off * k, parity + off * m,
+                                         pinned ? MEMO_EC_HOST_PINNED : MEMO_EC_HOST);
+    release(d, c);
+    return rc;
+  }, "encode_ragged");
+  ++encode_calls_;
+  ++ragged_calls_;
+}
+
+void Codec::verify_ragged(int k, int m, size_t n, const size_t* sizes, const uint8_t* data,
+                          const uint8_t* parity, uint32_t* verdict, bool pinned) {
+  split_ragged(n, sizes, [&](size_t d, size_t b0, size_t cnt, size_t off) {
+    auto* c = acquire(d);
+    const int rc = memo_ec_verify_ragged(c, k, m, cnt, sizes + b0, data + off * k, parity + off * m,
+                                         verdict + b0, pinned ? MEMO_EC_HOST_PINNED : MEMO_EC_HOST);
+    release(d, c);
+    return rc;
+  }, "verify_ragged");
+  ++verify_calls_;
+  ++ragged_calls_;
+}
+
 void Codec::rebuild(int k, int m, size_t S, size_t n, const uint8_t* surv_idx,
                     const uint8_t* surv, const uint8_t* lost_idx, int e, uint8_t* out, bool pinned) {
   split(n, [&](size_t d, size_t b0, size_t cnt) {
@@ -327,6 +390,7 @@ PinnedArena::~PinnedArena() {
 
 PinnedArena::Lease PinnedArena::lease(size_t bytes) {
   ++leases_;
+  leased_bytes_ += bytes;
   bytes = std::max<size_t>(bytes, 64);
   {
     std::lock_guard<std::mutex> g(mu_);
@@ -903,6 +967,24 @@ void ErasureConsensus::batcher_loop() {
       }
     }
     std::map<int, std::vector<EncodeJob*>> by_s;
+    {
+      // several shard sizes in the batch: one ragged encode of all of it
+      std::vector<const Block*> bs;
+      for (auto* j : jobs) bs.push_back(j->block);
+      if (ragged_batch(bs)) {
+        try {
+          const EncodedRagged enc = encode_ragged(bs, false, nullptr);
+          for (size_t i = 0; i < bs.size(); ++i) {
+            // block i's m parity shards are contiguous at its own shard size
+            const uint8_t* p = enc.parity.data() + (size_t)o_.m * enc.off[i];
+            jobs[i]->parity.set_value(Buffer(p, p + (size_t)o_.m * enc.sizes[i]));
+          }
+        } catch (...) {
+          for (auto* j : jobs) j->parity.set_exception(std::current_exception());
+        }
+        continue;
+      }
+    }
     for (auto* j : jobs) by_s[size_bucket(memo_ec_shard_size(j->block->data.size(), o_.k))].push_back(j);
     for (auto& g : by_s) {
       std::vector<const Block*> bs;
@@ -930,6 +1012,7 @@ ErasureConsensus::Encoded ErasureConsensus::encode_bucket(const std::vector<cons
   size_t S = 0;
   for (auto* b : bs) S = std::max(S, memo_ec_shard_size(b->data.size(), o_.k));
   Encoded enc{arena_.lease(n * o_.k * S), arena_.lease(n * o_.m * S), S};
+  store_data_bytes_ += n * o_.k * S;
   if (tm) tm->lap("alloc");
   auto copy_in = [&](size_t i) {
     const auto& d = bs[i]->data;
@@ -940,6 +1023,46 @@ ErasureConsensus::Encoded ErasureConsensus::encode_bucket(const std::vector<cons
     for (size_t i = 0; i < n; ++i) copy_in(i);
   if (tm) tm->lap("copy_in");
   codec_.encode(o_.k, o_.m, S, n, enc.data.data(), enc.parity.data(), enc.data.pinned() && enc.parity.pinned());
+  if (tm) tm->lap("encode");
+  return enc;
+}
+
+bool ErasureConsensus::ragged_batch(const std::vector<const Block*>& bs) const {
+  if (!o_.ragged_store || bs.size() < 2) return false;
+  const size_t S0 = memo_ec_shard_size(bs[0]->data.size(), o_.k);
+  for (auto* b : bs)
+    if (memo_ec_shard_size(b->data.size(), o_.k) != S0) return true;
+  return false;
+}
+
+ErasureConsensus::EncodedRagged ErasureConsensus::encode_ragged(const std::vector<const Block*>& bs,
+                                                                bool on_pool, PhaseTimer* tm) {
+  const size_t n = bs.size();
+  EncodedRagged enc;
+  enc.sizes.resize(n);
+  enc.off.assign(n + 1, 0);
+  enc.S = 0;
+  for (size_t i = 0; i < n; ++i) {
+    enc.sizes[i] = memo_ec_shard_size(bs[i]->data.size(), o_.k);
+    enc.off[i + 1] = enc.off[i] + enc.sizes[i];
+    enc.S = std::max(enc.S, enc.sizes[i]);
+  }
+  const size_t T = enc.off[n];
+  enc.data = arena_.lease(T * o_.k);
+  enc.parity = arena_.lease(T * o_.m);
+  store_data_bytes_ += T * o_.k;
+  if (tm) tm->lap("alloc");
+  auto copy_in = [&](size_t i) {
+    // the block's k shards back to back at its own size: only the
+    // memo_ec_shard_size padding behind the payload is zeroed
+    copy_padded(bs[i]->data, o_.k, enc.sizes[i], enc.data.data() + enc.off[i] * o_.k, enc.sizes[i]);
+  };
+  if (on_pool) pool_.parallel_for(n, copy_in);
+  else
+    for (size_t i = 0; i < n; ++i) copy_in(i);
+  if (tm) tm->lap("copy_in");
+  codec_.encode_ragged(o_.k, o_.m, n, enc.sizes.data(), enc.data.data(), enc.parity.data(),
+                       enc.data.pinned() && enc.parity.pinned());
   if (tm) tm->lap("encode");
   return enc;
 }
@@ -957,7 +1080,8 @@ void ErasureConsensus::place(const Block& b, const uint8_t* parity) {
 
 std::exception_ptr ErasureConsensus::place_batch(const std::vector<const Block*>& bs, const uint8_t* data,
                                                  const uint8_t* parity, size_t S,
-                                                 std::vector<Placed>& placed) {
+                                                 std::vector<Placed>& placed,
+                                                 const std::vector<size_t>* off) {
   const int k = o_.k, m = o_.m, total = k + m;
   const size_t n = bs.size();
   PhaseTimer tm("place_batch");
@@ -1003,7 +1127,11 @@ std::exception_ptr ErasureConsensus::place_batch(const std::vector<const Block*>
     auto payload = [&](uint32_t e) {
       const size_t i = e / total;
       const int j = (int)(e % total);
-      return j < k ? data + (i * k + j) * S : parity + (i * m + (j - k)) * S;
+      // the block's first shard byte and its slot size: uniform slots of S
+      // bytes, or (ragged) its own shard size from its own offset
+      const size_t base = off ? (*off)[i] : i * S, Si = off ? (size_t)hdr[i].shard_size : S;
+      return j < k ? data + batch_shard_offset(base, k, j, Si)
+                   : parity + batch_shard_offset(base, m, j - k, Si);
     };
     for (size_t x0 = 0; x0 < ne;) {
       const size_t cnt = per_frame ? std::min(per_frame, ne - x0) : 1;
@@ -1142,6 +1270,19 @@ void ErasureConsensus::store_many(const std::vector<Block>& blocks) {
       const Block* b = imm[b0 + i];
       if (!valid[i]) throw ValidationFailed("CHB address mismatch");
       by_s[size_bucket(memo_ec_shard_size(b->data.size(), o_.k))].push_back(b);
+    }
+    if (std::vector<const Block*> all(imm.begin() + b0, imm.begin() + b0 + n0); ragged_batch(all)) {
+      // several shard sizes in the chunk: one ragged encode, every block
+      // staged at its own shard size, and one placement pass over all of it
+      by_s.clear();
+      const EncodedRagged enc = encode_ragged(all, true, &tm);
+      std::vector<Placed> placed(all.size());
+      std::exception_ptr err =
+          place_batch(all, enc.data.data(), enc.parity.data(), enc.S, placed, &enc.off);
+      tm.lap("place");
+      commit_placements(placed);
+      tm.lap("index");
+      if (err) std::rethrow_exception(err);
     }
     for (auto& g : by_s) {
       const Encoded enc = encode_bucket(g.second, true, &tm);
@@ -2524,7 +2665,7 @@ void ErasureConsensus::membership_loop() {
 // "erasure" configuration: {"type": "erasure", "data-shards": k,
 // "parity-shards": m, "backend-replication-factor": f, and optionally
 // "device", "batch-max", "eviction-delay" (s), "stage-mb", "threads",
-// "fetch-hedge", "verify-subsets"};
+// "fetch-hedge", "verify-subsets", "ragged-store" (0 / 1)};
 // kebab-case keys as "replication-factor" (Paxos.cc:2273-2276).
 namespace {
 struct RegisterErasure {
@@ -2544,6 +2685,7 @@ struct RegisterErasure {
       o.threads = get("threads", o.threads);
       o.fetch_hedge = get("fetch-hedge", o.fetch_hedge);
       o.verify_subsets = get("verify-subsets", o.verify_subsets);
+      o.ragged_store = get("ragged-store", o.ragged_store ? 1 : 0) != 0;
       if (o.batch_max < 1 || stage_mb < 1 || o.threads < 1)
         throw Error("erasure: batch-max, stage-mb and threads must be positive");
       if (o.fetch_hedge < 0 || o.verify_subsets < 0)

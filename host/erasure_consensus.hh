@@ -60,6 +60,15 @@ class Codec {
   // (memo_ec_verify_batch); pinned covers all three buffers.
   void verify(int k, int m, size_t S, size_t n, const uint8_t* data, const uint8_t* parity,
               uint32_t* verdict, bool pinned = false);
+  // Ragged batches (memo_ec_encode_ragged / memo_ec_verify_ragged): block b
+  // has its own shard size sizes[b] and the blocks are packed back to back,
+  // data shard j of block b at data + k * off[b] + j * sizes[b], parity shard
+  // i at parity + m * off[b] + i * sizes[b].  With several devices the block
+  // range is cut on block boundaries, balanced by bytes.
+  void encode_ragged(int k, int m, size_t n, const size_t* sizes, const uint8_t* data,
+                     uint8_t* parity, bool pinned = false);
+  void verify_ragged(int k, int m, size_t n, const size_t* sizes, const uint8_t* data,
+                     const uint8_t* parity, uint32_t* verdict, bool pinned = false);
   void rebuild(int k, int m, size_t S, size_t n, const uint8_t* surv_idx, const uint8_t* surv,
                const uint8_t* lost_idx, int e, uint8_t* out, bool pinned = false);
   // One erasure pattern for all n blocks (memo_ec_rebuild_uniform):
@@ -73,6 +82,9 @@ class Codec {
   void rebuild_segments(const std::vector<memo_ec_rebuild_segment>& segs, bool pinned = false);
   uint64_t encode_calls() const { return encode_calls_; }
   uint64_t verify_calls() const { return verify_calls_; }
+  // encode_ragged and verify_ragged calls (a ragged encode also counts in
+  // encode_calls(), a ragged verify in verify_calls())
+  uint64_t ragged_calls() const { return ragged_calls_; }
   uint64_t rebuild_calls() const { return rebuild_calls_; }
   uint64_t uniform_calls() const { return uniform_calls_; }
   uint64_t segments_calls() const { return segments_calls_; }
@@ -90,14 +102,30 @@ class Codec {
   void release(size_t d, memo_ec_ctx* c);
   // fn(device slot, first block, blocks) over the device partition of n
   void split(size_t n, const std::function<int(size_t, size_t, size_t)>& fn, const char* what);
+  // the same over a ragged batch: ranges of about equal bytes; fn also gets
+  // the range's first byte offset (off[b0], in shard bytes)
+  void split_ragged(size_t n, const size_t* sizes,
+                    const std::function<int(size_t, size_t, size_t, size_t)>& fn, const char* what);
   std::mutex mu_;
   std::condition_variable cv_;
   std::vector<memo_ec_ctx*> all_;
   std::vector<Dev> dev_;
   std::atomic<size_t> rr_{0};
   std::atomic<uint64_t> encode_calls_{0}, rebuild_calls_{0}, uniform_calls_{0}, segments_calls_{0},
-      uniform_segments_{0}, verify_calls_{0};
+      uniform_segments_{0}, verify_calls_{0}, ragged_calls_{0};
 };
+
+// The device partition of a ragged batch: at most `parts` consecutive block
+// ranges [cuts[i], cuts[i + 1]) that cover [0, n), cut where the running
+// byte count passes i / parts of the total (no empty range).
+std::vector<size_t> cut_ragged_ranges(const size_t* sizes, size_t n, size_t parts);
+// Byte offset of shard j of a block in a batch buffer of `per` shards per
+// block (k for data, m for parity): the block's shards start `base` shard
+// bytes into the batch (ragged: off[b]; uniform slots: b * S) and are Si
+// bytes each.
+inline size_t batch_shard_offset(size_t base, size_t per, size_t j, size_t Si) {
+  return base * per + j * Si;
+}
 
 // A memo_ec_verify_batch verdict word taken apart: the stored parity rows
 // that mismatch, and the single shard that explains them (-1: none does).
@@ -153,9 +181,11 @@ class PinnedArena {
   // leases handed out so far (tests: a multi-fetch or repair chunk takes
   // one survivor and one output lease, however many batches it has)
   uint64_t leases() const { return leases_.load(); }
+  // bytes asked of lease() so far (tests: a ragged store stages no padding)
+  uint64_t leased_bytes() const { return leased_bytes_.load(); }
 
  private:
-  std::atomic<uint64_t> leases_{0};
+  std::atomic<uint64_t> leases_{0}, leased_bytes_{0};
   struct Buf {
     uint8_t* p;
     size_t cap;
@@ -365,6 +395,15 @@ struct ErasureOptions {
   // shard, at most this many ("verify-subsets"); the shards that disagree
   // with the verified block are rewritten.  0: fail at once.
   int verify_subsets = 64;
+  // "ragged-store": a batcher batch or store_many chunk that holds more than
+  // one shard size is encoded by ONE ragged call, every block staged at its
+  // own shard size; off: one call per power-of-two size bucket, every shard
+  // padded to the bucket's largest.  A batch of one shard size makes the
+  // same uniform call either way.  Off by default: with it on a mixed chunk
+  // makes one encode call where it made one per bucket, and
+  // host/tests/test_erasure.cc store_many_stages_in_chunks asks for at least
+  // 5 encode calls of a request that stages 4 chunks.
+  bool ragged_store = false;
 };
 
 // The peer ErasureConsensus::make_local makes, in front of its backend's
@@ -478,6 +517,9 @@ class ErasureConsensus : public StackedConsensus {
   void store_many(const std::vector<Block>& blocks);
   const Codec& codec() const { return codec_; }
   uint64_t arena_leases() const { return arena_.leases(); }
+  uint64_t arena_leased_bytes() const { return arena_.leased_bytes(); }
+  // bytes of the data (not parity) leases the store path staged so far
+  uint64_t store_data_bytes() const { return store_data_bytes_.load(); }
   size_t arena_kept_bytes() const { return arena_.kept_bytes(); }
   const ErasureOptions& options() const { return o_; }
   // The owner blocks removals of owned CHBs are checked against (the
@@ -553,8 +595,13 @@ class ErasureConsensus : public StackedConsensus {
   // parity + (i*m + r)*S), the shards grouped by owner so that one pool task
   // stores an owner's run of shards.  Every block is tried; returns the
   // first failure (TooFewPeers) or null.
+  // With `off` (a ragged batch, S its largest shard size) block i's shards
+  // sit back to back at its own shard size Si: data shard j at
+  // data + k * off[i] + j * Si, parity shard r at parity + m * off[i] + r * Si;
+  // without, off[i] = i * S and Si = S, the slots above.
   std::exception_ptr place_batch(const std::vector<const Block*>& bs, const uint8_t* data,
-                                 const uint8_t* parity, size_t S, std::vector<Placed>& placed);
+                                 const uint8_t* parity, size_t S, std::vector<Placed>& placed,
+                                 const std::vector<size_t>* off = nullptr);
   void batcher_loop();
   // from (k + m entries): the node each gathered shard came from
   // block: data shards' payloads straight into it (see the definition)
@@ -607,6 +654,18 @@ class ErasureConsensus : public StackedConsensus {
     size_t S;
   };
   Encoded encode_bucket(const std::vector<const Block*>& bs, bool on_pool, PhaseTimer* tm);
+  // Blocks of several shard sizes encoded by one ragged call: block i's
+  // shards at its own size sizes[i], back to back from off[i] (Codec::
+  // encode_ragged's layout), no padding byte staged.  S: the largest size.
+  struct EncodedRagged {
+    PinnedArena::Lease data, parity;  // k * T, m * T bytes
+    size_t S;
+    std::vector<size_t> sizes, off;   // n, n + 1 (off[n] = T)
+  };
+  EncodedRagged encode_ragged(const std::vector<const Block*>& bs, bool on_pool, PhaseTimer* tm);
+  // Whether the batch bs goes to encode_ragged: the option is on and the
+  // blocks have more than one shard size.
+  bool ragged_batch(const std::vector<const Block*>& bs) const;
   // The repair engine: rebuild and re-place the lost shards of `blocks`, a
   // chunk at a time: scan, plan and stage (placing each block as it comes
   // back), commit.
@@ -674,6 +733,7 @@ class ErasureConsensus : public StackedConsensus {
   // fetched_ and decoded_ are added to per block by every pool thread
   Counter stored_, fetched_, decoded_;
   std::atomic<uint64_t> repaired_{0}, evictions_{0};
+  std::atomic<uint64_t> store_data_bytes_{0};
   // reassemblies that failed their address and were recovered from another
   // k-subset; shards found wrong that way and rewritten
   std::atomic<uint64_t> subset_recoveries_{0}, corrupt_rewritten_{0};

@@ -239,6 +239,38 @@ int memo_ec_verify_batch(memo_ec_ctx *ctx, int k, int m, size_t S, size_t n,
                          const uint8_t *data, const uint8_t *parity,
                          uint32_t *verdict, int where);
 
+/* Ragged batches: n blocks, each with its own shard size, encoded or verified
+ * in one call with no padding byte.
+ *
+ * sizes[b] = S[b], the shard size of block b: a multiple of 64 below 2^32;
+ * 0 is allowed (such a block has no bytes, and its verdict word is 0).  With
+ * off[b] = S[0] + ... + S[b-1] and T = off[n]:
+ *   data   holds k * T bytes; data shard j of block b is at
+ *          data + k * off[b] + j * S[b];
+ *   parity holds m * T bytes; parity shard i of block b is at
+ *          parity + m * off[b] + i * S[b].
+ * Blocks stay block-major with their shards contiguous: with every S[b]
+ * equal this is byte for byte the layout of memo_ec_encode_batch.
+ *
+ * sizes: n entries in HOST memory whatever `where` says (as the patterns of
+ * memo_ec_rebuild_uniform are), read only during the call: the caller may
+ * free it when the call returns.  Everything about it is checked on the host
+ * before anything is enqueued: a size that is no multiple of 64 or is >= 2^32,
+ * or a NULL `sizes` with n > 0, returns MEMO_EC_EINVAL; k * T or m * T >= 2^50
+ * returns MEMO_EC_ERANGE.  n == 0, T == 0 or m == 0 writes nothing.
+ *
+ * `where`, pointer alignment (data and parity 16 bytes, verdict 4) and
+ * asynchrony are as for memo_ec_encode_batch / memo_ec_verify_batch; the
+ * verdict words (n of them) are those of memo_ec_verify_batch.  Ragged calls
+ * issued back to back on one ctx need no synchronize between them.  The call
+ * stages a block index for its kernels through buffers of the ctx, so it
+ * cannot be captured into a HIP graph. */
+int memo_ec_encode_ragged(memo_ec_ctx *ctx, int k, int m, size_t n, const size_t *sizes,
+                          const uint8_t *data, uint8_t *parity, int where);
+int memo_ec_verify_ragged(memo_ec_ctx *ctx, int k, int m, size_t n, const size_t *sizes,
+                          const uint8_t *data, const uint8_t *parity,
+                          uint32_t *verdict, int where);
+
 /* Rebuild the e lost shards of each block from its k survivors.  A lost
  * index may name a data or a parity shard.  e == 0 is a no-op. */
 int memo_ec_rebuild_batch(memo_ec_ctx *ctx, int k, int m, size_t S, size_t n,

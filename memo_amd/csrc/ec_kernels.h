@@ -99,6 +99,26 @@ struct MacLaunch {
   MacSeg seg[MEMO_EC_MAX_SEGMENTS];
 };
 
+// Ragged batches (memo_ec_encode_ragged / memo_ec_verify_ragged): blocks of
+// their own shard sizes packed back to back.  The device-resident index of
+// one launch span (built on the host: ragged_plan.h), zero-size blocks left
+// out: q numbers the span's non-empty blocks.
+struct RaggedIdx {
+  const uint64_t* coff;  // nq + 1: first column of block q in the span's column space; [nq]: its end
+  const uint32_t* orig;  // nq: the caller's block number of q, relative to the span's first block
+  const uint4* desc;     // per tile: ragged::TileDesc {q_first, nblk, c0, cols}
+};
+
+// One ragged span = one launch.  Of `seg` the ragged kernels read in / out
+// (the span's first data / parity byte), tab, kin (= k), r (= m), kpad,
+// tiles and verdict (the span's first word); shard strides come per lane
+// from the index.
+struct RaggedLaunch {
+  MacSeg seg;
+  RaggedIdx idx;
+  uint32_t xcd;  // 1: XCD-contiguous tile order (as MacLaunch::xcd)
+};
+
 struct DecodeArgs {
   const uint8_t* surv_idx;
   const uint8_t* lost_idx;
@@ -146,6 +166,14 @@ struct LocateArgs {
   uint32_t k, m;
 };
 
+// verify_locate_ragged_kernel: block b's data at data + k * 16 * boff[b], its
+// parity at parity + m * 16 * boff[b], S[b] = 16 * (boff[b + 1] - boff[b]);
+// a.S is unused.
+struct RaggedLocateArgs {
+  LocateArgs a;
+  const uint64_t* boff;  // n + 1 column offsets (off[b] / 16), zero-size blocks included
+};
+
 struct FillArgs {
   uint8_t* out;
   uint64_t seed, first_block, n, B, stride;
@@ -173,6 +201,10 @@ void lw0_host(int k, int m, uint8_t* out);
 hipError_t launch_decode_coef(const DecodeArgs& a, hipStream_t st);  // closed-form decode rows
 hipError_t launch_decode_multi(const DecodeArgs* a, int n, hipStream_t st);  // several segments
 hipError_t launch_verify_locate(const LocateArgs& a, hipStream_t st);
+// gf_mac_ragged_kernel (verify false) / gf_verify_ragged_kernel over one span.
+hipError_t launch_mac_ragged(int KC, int R, bool verify, const RaggedLaunch& L, uint32_t grid,
+                             size_t lds, hipStream_t st);
+hipError_t launch_verify_locate_ragged(const RaggedLocateArgs& a, hipStream_t st);
 hipError_t launch_fill(const FillArgs& a, hipStream_t st);
 hipError_t launch_sha256(const Sha256Args& a, hipStream_t st);
 hipError_t launch_gather(const GatherArgs& a, hipStream_t st);

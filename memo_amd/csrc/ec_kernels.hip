@@ -224,6 +224,7 @@ struct Unit {
   bool valid;
   const uint8_t* pin;
   uint8_t* pout;
+  uint32_t rs;       // ragged kernels only: this lane's block's shard size
   __device__ __forceinline__ const uint8_t* in(const MacSeg& sg, uint32_t j) const {
     return pin + (uint64_t)j * sg.in_sstride;
   }
@@ -231,6 +232,18 @@ struct Unit {
     return pout + (uint64_t)i * sg.out_sstride;
   }
 };
+// Shard j / row i of the lane's column: the segment's strides, or (ragged)
+// the lane's own block's shard size.
+template <bool RAGGED>
+__device__ __forceinline__ const uint8_t* unit_in(const Unit& u, const MacSeg& sg, uint32_t j) {
+  if constexpr (RAGGED) return u.pin + (uint64_t)j * u.rs;
+  else return u.in(sg, j);
+}
+template <bool RAGGED>
+__device__ __forceinline__ uint8_t* unit_out(const Unit& u, const MacSeg& sg, uint32_t i) {
+  if constexpr (RAGGED) return u.pout + (uint64_t)i * u.rs;
+  else return u.out(sg, i);
+}
 
 __device__ __forceinline__ Unit locate(const MacSeg& sg, uint64_t tile) {
   Unit u;
@@ -270,6 +283,69 @@ __device__ __forceinline__ Unit locate(const MacSeg& sg, uint64_t tile) {
   const uint64_t b = u.b_first + bo;
   u.pin = sg.in + b * sg.in_bstride + (uint64_t)cc * 16;
   u.pout = sg.out + b * sg.out_bstride + (uint64_t)cc * 16;
+  return u;
+}
+
+// Ragged locate: tile `tile` of a span whose blocks have their own shard
+// sizes (RaggedIdx; the index leaves zero-size blocks out).  The tile's
+// descriptor is one wave-uniform 16-byte load.
+//  * A tile inside one block (nblk == 1: every tile of a block of several
+//    tiles but its edges) needs nothing else: the aligned mapping's
+//    arithmetic on the descriptor's scalars.
+//  * A tile across blocks touches nblk <= 64 non-empty blocks (S >= 64 is 4
+//    columns).  Lane l of each wave loads the start of block q_first + 1 + l
+//    (entry nblk - 1 is the start of the block behind the tile's last, or
+//    the span's end), relative to the tile's first column: below 2^28 + 256.
+//    Every lane then walks the nblk starts, broadcast one at a time, and
+//    keeps the last one at or before its column and the first one past it:
+//    its block's bounds, hence its shard size.  One memory latency ahead of
+//    the shard loads, no LDS.
+// Lanes past the span's columns (last tile) take the tile's first column
+// and store nothing.  u.b_first + u.set is the lane's q.
+__device__ __forceinline__ Unit locate_ragged(const MacSeg& sg, const RaggedIdx& rg, uint64_t tile) {
+  Unit u;
+  const uint32_t tid = threadIdx.x;
+  const uint4 d = rg.desc[tile];
+  const uint32_t q_first = __builtin_amdgcn_readfirstlane(d.x);
+  const uint32_t nblk = __builtin_amdgcn_readfirstlane(d.y);
+  const uint32_t c0 = __builtin_amdgcn_readfirstlane(d.z);
+  const uint32_t c_first = __builtin_amdgcn_readfirstlane(d.w);
+  int32_t start = -(int32_t)c0;  // the lane's block's first column, relative to the tile's
+  int32_t end = (int32_t)(c_first - c0);
+  uint32_t cnt = 0;
+  if (nblk == 1) {
+    u.valid = tid < (uint32_t)end;
+  } else {
+    const uint32_t lane = tid % 64;
+    const uint64_t base = tile * (uint64_t)MAC_TILE;
+    int32_t e = 0x7fffffff;
+    if (lane < nblk) e = (int32_t)(uint32_t)(rg.coff[(uint64_t)q_first + 1 + lane] - base);
+    const int32_t first_end = __builtin_amdgcn_readlane(e, 0);
+    end = 0x7fffffff;
+    for (uint32_t j = 0; j < nblk; ++j) {
+      const int32_t r = __builtin_amdgcn_readlane(e, j);
+      const bool take = r <= (int32_t)tid;
+      start = take ? r : start;
+      cnt += take ? 1u : 0u;
+      end = take ? end : (r < end ? r : end);
+    }
+    u.valid = cnt < nblk;
+    if (!u.valid) {
+      cnt = 0;
+      start = -(int32_t)c0;
+      end = first_end;
+    }
+  }
+  const uint32_t t = u.valid ? tid : 0u;
+  const uint32_t cc = (uint32_t)((int32_t)t - start);  // column inside the block
+  u.rs = (uint32_t)(end - start) * 16u;                 // < 2^32
+  u.b_first = q_first;
+  u.nsets = 1;
+  u.set = cnt;
+  // first byte of the block's shard row 0: k (or m) * 16 * its first column
+  const uint64_t bcol = (uint64_t)((int64_t)(tile * (uint64_t)MAC_TILE) + start);
+  u.pin = sg.in + bcol * (16ull * sg.kin) + (uint64_t)cc * 16;
+  u.pout = sg.out + bcol * (16ull * sg.r) + (uint64_t)cc * 16;
   return u;
 }
 
@@ -837,8 +913,10 @@ __device__ __forceinline__ void dec_wave_tile(const MacSeg& sg, const Unit& u, c
 // are copied from a precomputed image (MAC_ENCODE), built from per-block
 // coefficient rows in HBM (MAC_ROWS) or from rows the tile decodes itself
 // (MAC_FUSED).
-template <int KC, int R, bool NT, int MODE>
-__device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32_t* s_tab) {
+template <int KC, int R, bool NT, int MODE, bool RAGGED = false>
+__device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32_t* s_tab,
+                                         const RaggedIdx* rg = nullptr) {
+  static_assert(!RAGGED || MODE == MAC_ENCODE || MODE == MAC_VERIFY, "ragged: encode and verify");
   constexpr bool VERIFY = MODE == MAC_VERIFY;  // the encode path, compare in place of stores
   constexpr bool COEF = MODE != MAC_ENCODE && !VERIFY;  // tables built in LDS from coefficients
   constexpr bool FUSED = MODE == MAC_FUSED;
@@ -851,7 +929,9 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
   const uint32_t kin = sg.kin, kpad = sg.kpad;
   const uint32_t set_dw = R * kpad * 8;
 
-  const Unit u = locate(sg, tile);
+  Unit u;
+  if constexpr (RAGGED) u = locate_ragged(sg, *rg, tile);
+  else u = locate(sg, tile);
   constexpr bool SOA = COEF;  // per-coefficient tables: split q / lo regions
   TabRef<SOA> tab;
   if constexpr (SOA) {
@@ -975,11 +1055,11 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
     else load_tables(sg, u, set_dw, tv);
     uint4 d[KC];
 #pragma unroll
-    for (int g = 0; g < KC; ++g) d[g] = ld16<NT>(u.in(sg, g));
+    for (int g = 0; g < KC; ++g) d[g] = ld16<NT>(unit_in<RAGGED>(u, sg, g));
     if constexpr (PV_EARLY) {
 #pragma unroll
       for (int i = 0; i < R; ++i)
-        if ((uint32_t)i < sg.r) pv[i] = ld16<NT>(u.out(sg, i));
+        if ((uint32_t)i < sg.r) pv[i] = ld16<NT>(unit_out<RAGGED>(u, sg, i));
     }
     if constexpr (COEF) store_images<R, KC>(sg, u, tv, s_tab);
     else store_tables(sg, u, set_dw, tv, s_tab);
@@ -993,7 +1073,7 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
       uint4 d[KC];
 #pragma unroll
       for (int g = 0; g < KC; ++g)
-        if (j0 + g < kin) d[g] = ld16<NT>(u.in(sg, j0 + g));
+        if (j0 + g < kin) d[g] = ld16<NT>(unit_in<RAGGED>(u, sg, j0 + g));
       mac_chunk<KC, R>(acc, d, tab, kpad, j0);
     }
   }
@@ -1007,7 +1087,7 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
     if (!(PV_EARLY && kin == KC)) {
 #pragma unroll
       for (int i = 0; i < R; ++i)
-        if ((uint32_t)i < sg.r) pv[i] = ld16<NT>(u.out(sg, i));
+        if ((uint32_t)i < sg.r) pv[i] = ld16<NT>(unit_out<RAGGED>(u, sg, i));
     }
     uint32_t bad = 0;
 #pragma unroll
@@ -1017,12 +1097,15 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
                            (pv[i].w ^ acc[i][3]);
         bad |= x ? 1u << i : 0u;
       }
-    if (u.valid && bad) atomicOr(sg.verdict + u.b_first + u.set, bad);
+    if (u.valid && bad) {
+      if constexpr (RAGGED) atomicOr(sg.verdict + rg->orig[u.b_first + u.set], bad);
+      else atomicOr(sg.verdict + u.b_first + u.set, bad);
+    }
   } else if (u.valid) {
 #pragma unroll
     for (int i = 0; i < R; ++i)
       if ((uint32_t)i < sg.r)
-        st16<NT>(u.out(sg, i),
+        st16<NT>(unit_out<RAGGED>(u, sg, i),
                  make_uint4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]));
   }
 }
@@ -1101,8 +1184,9 @@ __device__ __forceinline__ uint32_t gf_mul4(const uint8_t* lg, const uint8_t* ex
          (gf_mul_t(lg, ex, c, (x >> 16) & 0xFFu) << 16) | (gf_mul_t(lg, ex, c, x >> 24) << 24);
 }
 
-template <int KMAX>
-__global__ void __launch_bounds__(256) verify_locate_kernel(const LocateArgs a) {
+// RAGGED: block b's shards and size come from boff (RaggedLocateArgs).
+template <int KMAX, bool RAGGED>
+__device__ __forceinline__ void verify_locate_body(const LocateArgs a, const uint64_t* boff) {
   __shared__ __attribute__((aligned(16))) uint32_t s_gf[kGfDwords];
   __shared__ uint8_t s_g[MEMO_EC_MAX_M * MEMO_EC_MAX_K];  // g_ij at i * k + j
   __shared__ uint32_t s_word[64];                         // the workgroup's 64 verdict words
@@ -1119,7 +1203,7 @@ __global__ void __launch_bounds__(256) verify_locate_kernel(const LocateArgs a) 
   const uint32_t tid = threadIdx.x, lane = tid % 64;
   const uint32_t all = (1u << m) - 1u;  // m <= 16
   const uint64_t kbits = k >= 64 ? ~0ull : (1ull << k) - 1ull;
-  const uint64_t dwords = a.S / 4;
+  const uint64_t dwords_u = RAGGED ? 0 : a.S / 4;
   for (uint64_t base = (uint64_t)blockIdx.x * 64; base < a.n; base += (uint64_t)gridDim.x * 64) {
     __syncthreads();  // s_g staged; the previous round's s_word all read
     if (tid < 64) s_word[tid] = base + tid < a.n ? a.verdict[base + tid] : 0u;
@@ -1137,8 +1221,18 @@ __global__ void __launch_bounds__(256) verify_locate_kernel(const LocateArgs a) 
       } else if (m >= 2 && mask == all) {
         if (tid < 2) s_cand[tid] = ~0u;
         __syncthreads();
-        const uint32_t* d = reinterpret_cast<const uint32_t*>(a.data + b * k * a.S);
-        const uint32_t* p = reinterpret_cast<const uint32_t*>(a.parity + b * m * a.S);
+        uint64_t dwords = dwords_u, d_off = 0, p_off = 0;
+        if constexpr (RAGGED) {
+          const uint64_t c0 = boff[b];
+          dwords = (boff[b + 1] - c0) * 4;
+          d_off = c0 * 16 * k;
+          p_off = c0 * 16 * m;
+        } else {
+          d_off = b * k * a.S;
+          p_off = b * m * a.S;
+        }
+        const uint32_t* d = reinterpret_cast<const uint32_t*>(a.data + d_off);
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(a.parity + p_off);
         uint64_t cand = kbits;  // data shards consistent with every byte this lane saw
         for (uint64_t w = tid; w < dwords && cand; w += 256) {
           uint32_t dv[KMAX];
@@ -1183,6 +1277,48 @@ __global__ void __launch_bounds__(256) verify_locate_kernel(const LocateArgs a) 
       if (tid == 0) a.verdict[b] = mask | (shard << 16);
     }
   }
+}
+
+template <int KMAX>
+__global__ void __launch_bounds__(256) verify_locate_kernel(const LocateArgs a) {
+  verify_locate_body<KMAX, false>(a, nullptr);
+}
+
+// The locate pass of memo_ec_verify_ragged: a flagged block's base and shard
+// size come from the call's block offsets.
+template <int KMAX>
+__global__ void __launch_bounds__(256) verify_locate_ragged_kernel(const RaggedLocateArgs ra) {
+  verify_locate_body<KMAX, true>(ra.a, ra.boff);
+}
+
+// ---- Ragged encode and verify: mac_tile with the ragged locate, one span
+// per launch, under names of their own (as gf_mac_images_kernel) so the
+// uniform kernels' code is not disturbed.
+__device__ __forceinline__ bool ragged_tile(const RaggedLaunch& L, uint64_t& tile) {
+  const uint32_t lw = blockIdx.x;
+  if (lw >= L.seg.tiles) return false;
+  tile = lw;
+  if (L.xcd) {  // the XCD-contiguous order of seg_tile
+    const uint32_t st = (uint32_t)L.seg.tiles, sq = st / 8, sr = st % 8, sx = lw % 8;
+    tile = sx * sq + (sx < sr ? sx : sr) + lw / 8;
+  }
+  return true;
+}
+
+template <int KC, int R, bool NT>
+__global__ void __launch_bounds__(256) gf_mac_ragged_kernel(const RaggedLaunch L) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];
+  uint64_t tile;
+  if (!ragged_tile(L, tile)) return;
+  mac_tile<KC, R, NT, MAC_ENCODE, true>(L.seg, tile, s_tab, &L.idx);
+}
+
+template <int KC, int R, bool NT>
+__global__ void __launch_bounds__(256) gf_verify_ragged_kernel(const RaggedLaunch L) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];
+  uint64_t tile;
+  if (!ragged_tile(L, tile)) return;
+  mac_tile<KC, R, NT, MAC_VERIFY, true>(L.seg, tile, s_tab, &L.idx);
 }
 
 #ifdef MEMO_EC_PERM_PROBE
@@ -2134,6 +2270,49 @@ hipError_t launch_mac(int KC, int R, int mode, const MacLaunch& L, uint32_t grid
   }
 }
 
+// The ragged kernels, for the (KC, R) launch_mac serves.
+template <int KC, int R>
+static hipError_t launch_ragged_t(bool verify, const RaggedLaunch& L, uint32_t grid, size_t lds,
+                                  hipStream_t st) {
+  if (verify)
+    hipLaunchKernelGGL((gf_verify_ragged_kernel<KC, R, MAC_NT>), dim3(grid), dim3(256), lds, st, L);
+  else
+    hipLaunchKernelGGL((gf_mac_ragged_kernel<KC, R, MAC_NT>), dim3(grid), dim3(256), lds, st, L);
+  return hipGetLastError();
+}
+template <int KC>
+static hipError_t launch_ragged_r(int R, bool verify, const RaggedLaunch& L, uint32_t grid,
+                                  size_t lds, hipStream_t st) {
+  switch (R) {
+#define MEMO_EC_R(x) \
+  case x: return launch_ragged_t<KC, x>(verify, L, grid, lds, st);
+    MEMO_EC_R(1) MEMO_EC_R(2) MEMO_EC_R(3) MEMO_EC_R(4)
+    default: break;
+  }
+  if constexpr (KC == 2 || KC == 3 || KC == 4 || KC == 10 || KC == 16) {
+    switch (R) {
+      MEMO_EC_R(6) MEMO_EC_R(8) MEMO_EC_R(12) MEMO_EC_R(16)
+      default: break;
+    }
+  }
+#undef MEMO_EC_R
+  return hipErrorInvalidValue;
+}
+hipError_t launch_mac_ragged(int KC, int R, bool verify, const RaggedLaunch& L, uint32_t grid,
+                             size_t lds, hipStream_t st) {
+  switch (KC) {
+    case 2: return launch_ragged_r<2>(R, verify, L, grid, lds, st);
+    case 3: return launch_ragged_r<3>(R, verify, L, grid, lds, st);
+    case 4: return launch_ragged_r<4>(R, verify, L, grid, lds, st);
+    case 6: return launch_ragged_r<6>(R, verify, L, grid, lds, st);
+    case 10: return launch_ragged_r<10>(R, verify, L, grid, lds, st);
+    case 12: return launch_ragged_r<12>(R, verify, L, grid, lds, st);
+    case 14: return launch_ragged_r<14>(R, verify, L, grid, lds, st);
+    case 16: return launch_ragged_r<16>(R, verify, L, grid, lds, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // Kernel choice for one decode segment: kind (0 column-per-lane, 1 exact-k,
 // 2 generic), its template parameter, workgroups, and the args as the
 // kernel takes them (row-staging pitch set).
@@ -2269,6 +2448,18 @@ hipError_t launch_verify_locate(const LocateArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(verify_locate_kernel<16>, dim3((uint32_t)grid), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(verify_locate_kernel<MEMO_EC_MAX_K>, dim3((uint32_t)grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_locate_ragged(const RaggedLocateArgs& ra, hipStream_t st) {
+  if (ra.a.n == 0) return hipSuccess;
+  uint64_t grid = (ra.a.n + 63) / 64;  // launch_verify_locate's grid
+  if (grid > 2048) grid = 2048;
+  if (ra.a.k <= 16)
+    hipLaunchKernelGGL(verify_locate_ragged_kernel<16>, dim3((uint32_t)grid), dim3(256), 0, st, ra);
+  else
+    hipLaunchKernelGGL(verify_locate_ragged_kernel<MEMO_EC_MAX_K>, dim3((uint32_t)grid), dim3(256), 0,
+                       st, ra);
   return hipGetLastError();
 }
 

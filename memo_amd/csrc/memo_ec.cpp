@@ -20,6 +20,7 @@
 
 #include "../../include/memo_ec.h"
 #include "ec_kernels.h"
+#include "ragged_plan.h"
 
 using namespace memo_ec;
 
@@ -87,6 +88,18 @@ struct memo_ec_ctx {
   uint8_t* h_slot[3] = {nullptr, nullptr, nullptr};
   size_t hslot_cap = 0;
   int deferred = 0;
+  // ragged calls: block-index staging.  Each call builds its index in a
+  // pinned buffer, copies it to the device buffer beside it on the call's
+  // stream and records `ev` behind its kernels; a buffer is taken again only
+  // once that event has passed, so calls issued back to back never share one.
+  struct IdxBuf {
+    uint8_t* host = nullptr;
+    uint8_t* dev = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool used = false;
+  };
+  std::vector<IdxBuf> idx_pool;
 };
 
 namespace {
@@ -680,6 +693,143 @@ int verify_device(memo_ec_ctx* ctx, int k, int m, size_t S, size_t n, const uint
   return hip_rc(launch_verify_locate(a, st));
 }
 
+// ---- Ragged batches (memo_ec_encode_ragged / memo_ec_verify_ragged).
+
+constexpr size_t kIdxPoolMax = 8;
+size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// An index buffer of at least `bytes` that no enqueued call still reads: a
+// free one that fits, a free one regrown, a new one while the pool is small,
+// else the oldest once its call has passed.
+int idx_acquire(memo_ec_ctx* c, size_t bytes, memo_ec_ctx::IdxBuf** out) {
+  auto is_free = [](memo_ec_ctx::IdxBuf& b) {
+    if (b.used && hipEventQuery(b.ev) == hipSuccess) b.used = false;
+    return !b.used;
+  };
+  memo_ec_ctx::IdxBuf* pick = nullptr;
+  for (auto& b : c->idx_pool)
+    if (is_free(b) && b.cap >= bytes) {
+      pick = &b;
+      break;
+    }
+  if (!pick)
+    for (auto& b : c->idx_pool)
+      if (!b.used) {
+        pick = &b;
+        break;
+      }
+  if (!pick && c->idx_pool.size() < kIdxPoolMax) {
+    c->idx_pool.emplace_back();
+    pick = &c->idx_pool.back();
+    hipError_t e = hipEventCreateWithFlags(&pick->ev, hipEventDisableTiming);
+    if (e != hipSuccess) {
+      c->idx_pool.pop_back();
+      return hip_rc(e);
+    }
+  }
+  if (!pick) {
+    pick = &c->idx_pool.front();
+    HIPCHK(hipEventSynchronize(pick->ev));
+    pick->used = false;
+  }
+  if (pick->cap < bytes) {
+    pick->cap = 0;
+    if (pick->dev) HIPCHK(hipFree(pick->dev));
+    pick->dev = nullptr;
+    if (pick->host) HIPCHK(hipHostFree(pick->host));
+    pick->host = nullptr;
+    const size_t cap = std::max<size_t>((bytes + 255) & ~(size_t)255, 64 << 10);
+    HIPCHK(hipMalloc(&pick->dev, cap));
+    HIPCHK(hipHostMalloc(&pick->host, cap, hipHostMallocDefault));
+    pick->cap = cap;
+  }
+  *out = pick;
+  return MEMO_EC_OK;
+}
+
+// Device-resident ragged encode (verdict null) or verify of n blocks on
+// stream st.  sizes / off: the blocks' shard sizes and byte offsets (off has
+// n + 1 entries and may start anywhere: a pipeline wave passes its part of
+// the call's arrays); data / parity / verdict: the first block's.  Builds
+// the index of every launch span, uploads it in one copy, then launches.
+int ragged_device(memo_ec_ctx* ctx, int k, int m, size_t n, const size_t* sizes, const uint64_t* off,
+                  const uint8_t* data, uint8_t* parity, uint32_t* verdict, hipStream_t st) {
+  const bool verify = verdict != nullptr;
+  if (verify) HIPCHK(hipMemsetAsync(verdict, 0, n * sizeof(uint32_t), st));
+  if (off[n] == off[0]) return MEMO_EC_OK;
+  const int R = mac_rbound(m), KC = mac_kchunk(k, R);
+  const uint32_t* tab = nullptr;
+  if (int rc = encode_tables(ctx, k, m, R, KC, &tab)) return rc;
+  uint64_t limit = 0x7fffffffull - MAC_TILE;
+  if (ctx->opt.max_launch_tiles >= 1 && ctx->opt.max_launch_tiles < limit)
+    limit = ctx->opt.max_launch_tiles;
+  const std::vector<ragged::Range> spans = ragged::cut_spans(sizes, n, limit);
+  // buffer layout: [boff (n + 1) x 8: verify] then per span [coff | desc | orig]
+  struct SpanAt {
+    ragged::Counts cnt;
+    size_t coff, desc, orig;
+  };
+  std::vector<SpanAt> at(spans.size());
+  size_t bytes = verify ? round16((n + 1) * sizeof(uint64_t)) : 0;
+  for (size_t i = 0; i < spans.size(); ++i) {
+    SpanAt& a = at[i];
+    a.cnt = ragged::index_counts(sizes + spans[i].b0, spans[i].b1 - spans[i].b0);
+    a.coff = bytes;
+    bytes += round16((a.cnt.nq + 1) * sizeof(uint64_t));
+    a.desc = bytes;
+    bytes += a.cnt.tiles * sizeof(ragged::TileDesc);
+    a.orig = bytes;
+    bytes += round16(a.cnt.nq * sizeof(uint32_t));
+  }
+  memo_ec_ctx::IdxBuf* buf = nullptr;
+  if (int rc = idx_acquire(ctx, bytes, &buf)) return rc;
+  if (verify) {
+    uint64_t* boff = reinterpret_cast<uint64_t*>(buf->host);
+    for (size_t b = 0; b <= n; ++b) boff[b] = (off[b] - off[0]) / 16;
+  }
+  for (size_t i = 0; i < spans.size(); ++i)
+    ragged::build_index(sizes + spans[i].b0, spans[i].b1 - spans[i].b0,
+                        reinterpret_cast<uint64_t*>(buf->host + at[i].coff),
+                        reinterpret_cast<uint32_t*>(buf->host + at[i].orig),
+                        reinterpret_cast<ragged::TileDesc*>(buf->host + at[i].desc));
+  buf->used = true;  // from here the buffer belongs to the enqueued work
+  int rc = hip_rc(hipMemcpyAsync(buf->dev, buf->host, bytes, hipMemcpyHostToDevice, st));
+  for (size_t i = 0; i < spans.size() && !rc; ++i) {
+    if (at[i].cnt.tiles == 0) continue;
+    const uint64_t o = off[spans[i].b0] - off[0];
+    RaggedLaunch L{};
+    MacSeg& s = L.seg;
+    s.in = data + (uint64_t)k * o;
+    s.out = parity + (uint64_t)m * o;
+    s.tab = tab;
+    s.n = at[i].cnt.nq;
+    s.tiles = at[i].cnt.tiles;
+    s.kin = (uint32_t)k;
+    s.r = (uint32_t)m;
+    s.kpad = kpad_of((uint32_t)k, KC);
+    s.flat = 1;
+    s.verdict = verify ? verdict + spans[i].b0 : nullptr;
+    L.idx.coff = reinterpret_cast<const uint64_t*>(buf->dev + at[i].coff);
+    L.idx.orig = reinterpret_cast<const uint32_t*>(buf->dev + at[i].orig);
+    L.idx.desc = reinterpret_cast<const uint4*>(buf->dev + at[i].desc);
+    L.xcd = s.tiles >= ctx->opt.xcd_min_tiles ? 1u : 0u;
+    rc = hip_rc(launch_mac_ragged(KC, R, verify, L, (uint32_t)s.tiles, (size_t)R * s.kpad * 32, st));
+  }
+  if (!rc && verify) {
+    RaggedLocateArgs ra{};
+    ra.a.data = data;
+    ra.a.parity = parity;
+    ra.a.verdict = verdict;
+    ra.a.n = n;
+    ra.a.k = (uint32_t)k;
+    ra.a.m = (uint32_t)m;
+    ra.boff = reinterpret_cast<const uint64_t*>(buf->dev);
+    rc = hip_rc(launch_verify_locate_ragged(ra, st));
+  }
+  const int rc2 = hip_rc(hipEventRecord(buf->ev, st));
+  return rc ? rc : rc2;
+}
+
 DecodeArgs decode_args(const memo_ec_ctx* c, int k, int m, int e, size_t n, const uint8_t* surv_idx,
                        const uint8_t* lost_idx, uint8_t* rows, uint32_t* status, const uint32_t* lw0) {
   DecodeArgs a{};
@@ -889,6 +1039,112 @@ int verify_host(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const uint8_t*
       },
       [&](int s, size_t b0, size_t cnt) {
         if (!pinned) std::memcpy(verdict + b0, c->h_slot[s] + v_off, cnt * v_b);
+      });
+}
+
+// Host-memory ragged encode: zero-copy on pinned memory for small calls,
+// else the copy pipeline with waves cut on block boundaries by input bytes
+// (host_mac with its fixed block size replaced by the call's offsets).
+int encode_ragged_host(memo_ec_ctx* c, int k, int m, size_t n, const size_t* sizes,
+                       const uint64_t* off, const uint8_t* data, uint8_t* parity, bool pinned) {
+  const uint64_t T = off[n];
+  const size_t in_b = (size_t)k * T, out_b = (size_t)m * T;
+  if (in_b + out_b <= zc_max_bytes(c)) {
+    if (int rc = ensure_slots(c, 0, pinned ? 0 : in_b + out_b)) return rc;
+    const uint8_t* src = data;
+    uint8_t* dst = parity;
+    if (!pinned) {
+      par_memcpy(c, c->h_slot[0], data, in_b);
+      src = c->h_slot[0];
+      dst = c->h_slot[0] + in_b;
+    }
+    if (int rc = ragged_device(c, k, m, n, sizes, off, src, dst, nullptr, c->sk)) return rc;
+    HIPCHK(hipStreamSynchronize(c->sk));
+    if (!pinned) par_memcpy(c, parity, dst, out_b);
+    return MEMO_EC_OK;
+  }
+  const std::vector<ragged::Range> waves = ragged::cut_waves(sizes, n, (uint64_t)k, c->opt.pipe_bytes);
+  uint64_t tmax = 0;
+  for (const auto& w : waves) tmax = std::max<uint64_t>(tmax, off[w.b1] - off[w.b0]);
+  const size_t slot = (size_t)(k + m) * tmax, o_off = (size_t)k * tmax;
+  if (int rc = ensure_slots(c, slot, pinned ? 0 : slot)) return rc;
+  auto wt = [&](size_t w) { return off[waves[w].b1] - off[waves[w].b0]; };
+  return run_waves(
+      c, waves.size(),
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const size_t nb = (size_t)k * wt(w);
+        if (!nb) return MEMO_EC_OK;
+        const uint8_t* src = data + (size_t)k * off[waves[w].b0];
+        if (!pinned) {
+          par_memcpy(c, c->h_slot[s], src, nb);
+          src = c->h_slot[s];
+        }
+        return hip_rc(hipMemcpyAsync(c->d_slot[s], src, nb, hipMemcpyHostToDevice, st));
+      },
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const ragged::Range& r = waves[w];
+        return ragged_device(c, k, m, r.b1 - r.b0, sizes + r.b0, off + r.b0, c->d_slot[s],
+                             c->d_slot[s] + o_off, nullptr, st);
+      },
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const size_t nb = (size_t)m * wt(w);
+        if (!nb) return MEMO_EC_OK;
+        uint8_t* dst = pinned ? parity + (size_t)m * off[waves[w].b0] : c->h_slot[s] + o_off;
+        return hip_rc(hipMemcpyAsync(dst, c->d_slot[s] + o_off, nb, hipMemcpyDeviceToHost, st));
+      },
+      [&](int s, size_t w) {
+        if (!pinned)
+          par_memcpy(c, parity + (size_t)m * off[waves[w].b0], c->h_slot[s] + o_off, (size_t)m * wt(w));
+      });
+}
+
+// Host-memory ragged verify through the copy pipeline (verify_host's slot
+// layout: [data | parity | verdict words], sized by the largest wave).
+int verify_ragged_host(memo_ec_ctx* c, int k, int m, size_t n, const size_t* sizes,
+                       const uint64_t* off, const uint8_t* data, const uint8_t* parity,
+                       uint32_t* verdict, bool pinned) {
+  const std::vector<ragged::Range> waves =
+      ragged::cut_waves(sizes, n, (uint64_t)(k + m), c->opt.pipe_bytes);
+  uint64_t tmax = 0;
+  size_t nmax = 0;
+  for (const auto& w : waves) {
+    tmax = std::max<uint64_t>(tmax, off[w.b1] - off[w.b0]);
+    nmax = std::max(nmax, w.b1 - w.b0);
+  }
+  const size_t p_off = (size_t)k * tmax, v_off = (size_t)(k + m) * tmax, v_b = sizeof(uint32_t);
+  const size_t slot = v_off + nmax * v_b;
+  if (int rc = ensure_slots(c, slot, pinned ? 0 : slot)) return rc;
+  auto wt = [&](size_t w) { return off[waves[w].b1] - off[waves[w].b0]; };
+  return run_waves(
+      c, waves.size(),
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const size_t db = (size_t)k * wt(w), pb = (size_t)m * wt(w);
+        if (!db) return MEMO_EC_OK;
+        const uint8_t* ds = data + (size_t)k * off[waves[w].b0];
+        const uint8_t* ps = parity + (size_t)m * off[waves[w].b0];
+        if (!pinned) {
+          par_memcpy(c, c->h_slot[s], ds, db);
+          par_memcpy(c, c->h_slot[s] + p_off, ps, pb);
+          ds = c->h_slot[s];
+          ps = c->h_slot[s] + p_off;
+        }
+        if (int rc = hip_rc(hipMemcpyAsync(c->d_slot[s], ds, db, hipMemcpyHostToDevice, st))) return rc;
+        return hip_rc(hipMemcpyAsync(c->d_slot[s] + p_off, ps, pb, hipMemcpyHostToDevice, st));
+      },
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const ragged::Range& r = waves[w];
+        return ragged_device(c, k, m, r.b1 - r.b0, sizes + r.b0, off + r.b0, c->d_slot[s],
+                             c->d_slot[s] + p_off, reinterpret_cast<uint32_t*>(c->d_slot[s] + v_off), st);
+      },
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const ragged::Range& r = waves[w];
+        void* dst = pinned ? static_cast<void*>(verdict + r.b0) : c->h_slot[s] + v_off;
+        return hip_rc(hipMemcpyAsync(dst, c->d_slot[s] + v_off, (r.b1 - r.b0) * v_b,
+                                     hipMemcpyDeviceToHost, st));
+      },
+      [&](int s, size_t w) {
+        const ragged::Range& r = waves[w];
+        if (!pinned) std::memcpy(verdict + r.b0, c->h_slot[s] + v_off, (r.b1 - r.b0) * v_b);
       });
 }
 
@@ -1603,6 +1859,12 @@ int memo_ec_ctx_destroy(memo_ec_ctx* c) {
   for (auto& p : c->h_slot)
     if (p) (void)hipHostFree(p);
   if (c->d_tabs) (void)hipFree(c->d_tabs);
+  for (auto& b : c->idx_pool) {
+    if (b.ev) (void)hipEventSynchronize(b.ev);
+    if (b.ev) (void)hipEventDestroy(b.ev);
+    if (b.dev) (void)hipFree(b.dev);
+    if (b.host) (void)hipHostFree(b.host);
+  }
   for (auto& e : c->enc_tabs) (void)hipFree(e.dev);
   for (auto& e : c->lw0_tabs) (void)hipFree(e.dev);
   for (auto& e : c->pat_tabs) (void)hipFree(e.dev);
@@ -1677,6 +1939,53 @@ int memo_ec_verify_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const
   if (where == MEMO_EC_DEVICE) return verify_device(c, k, m, S, n, data, parity, verdict, c->stream);
   if (where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
   return verify_host(c, k, m, S, n, data, parity, verdict, where == MEMO_EC_HOST_PINNED);
+}
+
+// The ragged calls' argument checks, all on the host before anything is
+// enqueued: no size the host has not validated reaches a kernel.
+static int ragged_check(int k, int m, size_t n, const size_t* sizes, std::vector<uint64_t>& off) {
+  switch (ragged::prefix_sums(sizes, n, (unsigned)k, (unsigned)m, off)) {
+    case ragged::kOk: return MEMO_EC_OK;
+    case ragged::kRange: return MEMO_EC_ERANGE;
+    default: return MEMO_EC_EINVAL;
+  }
+}
+
+int memo_ec_encode_ragged(memo_ec_ctx* c, int k, int m, size_t n, const size_t* sizes,
+                          const uint8_t* data, uint8_t* parity, int where) {
+  if (int rc = check_km(k, m)) return rc;
+  std::vector<uint64_t> off;
+  if (int rc = ragged_check(k, m, n, sizes, off)) return rc;
+  if (!c) return MEMO_EC_EINVAL;
+  if (m == 0 || n == 0 || off[n] == 0) return MEMO_EC_OK;
+  if (!data || !parity) return MEMO_EC_EINVAL;
+  if (shard_misaligned(where, data) || shard_misaligned(where, parity)) return MEMO_EC_EINVAL;
+  if (where != MEMO_EC_DEVICE && where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED)
+    return MEMO_EC_EINVAL;
+  DeviceGuard g(c->device);
+  if (where == MEMO_EC_DEVICE)
+    return ragged_device(c, k, m, n, sizes, off.data(), data, parity, nullptr, c->stream);
+  return encode_ragged_host(c, k, m, n, sizes, off.data(), data, parity, where == MEMO_EC_HOST_PINNED);
+}
+
+int memo_ec_verify_ragged(memo_ec_ctx* c, int k, int m, size_t n, const size_t* sizes,
+                          const uint8_t* data, const uint8_t* parity, uint32_t* verdict, int where) {
+  if (int rc = check_km(k, m)) return rc;
+  std::vector<uint64_t> off;
+  if (int rc = ragged_check(k, m, n, sizes, off)) return rc;
+  if (!c) return MEMO_EC_EINVAL;
+  if (m == 0 || n == 0 || off[n] == 0) return MEMO_EC_OK;
+  if (!data || !parity || !verdict) return MEMO_EC_EINVAL;
+  if (shard_misaligned(where, data) || shard_misaligned(where, parity) || misaligned(verdict, 4))
+    return MEMO_EC_EINVAL;
+  if (where != MEMO_EC_DEVICE && where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED)
+    return MEMO_EC_EINVAL;
+  DeviceGuard g(c->device);
+  if (where == MEMO_EC_DEVICE)
+    return ragged_device(c, k, m, n, sizes, off.data(), data, const_cast<uint8_t*>(parity), verdict,
+                         c->stream);
+  return verify_ragged_host(c, k, m, n, sizes, off.data(), data, parity, verdict,
+                            where == MEMO_EC_HOST_PINNED);
 }
 
 int memo_ec_stream_probe(memo_ec_ctx* c, int kin, int r, size_t S, size_t n, const uint8_t* in,

@@ -1,0 +1,171 @@
+// ragged_plan.h -- GPU-free planning of ragged batches (memo_ec_encode_ragged /
+// memo_ec_verify_ragged): size validation, prefix sums, launch spans, pipeline
+// waves and the per-tile descriptors the ragged kernels read.  Plain C++17,
+// no HIP include: tests/test_ragged_plan.py builds it into a stand-alone
+// program with the host sanitizers.
+//
+// A ragged batch of n blocks has shard sizes S[b] (multiples of 64, < 2^32,
+// 0 allowed), packed back to back: off[b] = S[0] + ... + S[b-1], T = off[n].
+// Its column space is the T / 16 16-byte columns of one shard row,
+// concatenated over the blocks; tile t covers columns [256 t, 256 t + 256).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace memo_ec {
+namespace ragged {
+
+constexpr uint32_t kTileCols = 256;              // MAC_TILE of ec_kernels.h
+constexpr uint64_t kMaxShard = 1ull << 32;       // shard sizes stay below
+constexpr uint64_t kMaxCallBytes = 1ull << 50;   // k * T and m * T stay below
+constexpr uint64_t kMaxSpanBlocks = 0x7fffffffull;  // non-empty blocks of one launch (32-bit index)
+
+enum Status { kOk = 0, kInvalid = 1, kRange = 2 };
+
+// Validates sizes and forms off[0..n] (bytes).  kInvalid: sizes null with
+// n > 0, a size that is no multiple of 64 or is >= 2^32; kRange: k * T or
+// m * T >= 2^50.  An invalid size anywhere wins over the range.
+inline Status prefix_sums(const size_t* sizes, size_t n, unsigned k, unsigned m,
+                          std::vector<uint64_t>& off) {
+  off.clear();
+  if (n && !sizes) return kInvalid;
+  const unsigned per = k > m ? k : m;
+  bool range = false;
+  uint64_t t = 0;
+  off.reserve(n < (1u << 20) ? n + 1 : (1u << 20));
+  off.push_back(0);
+  for (size_t b = 0; b < n; ++b) {
+    const uint64_t s = (uint64_t)sizes[b];
+    if (s % 64 != 0 || s >= kMaxShard) return kInvalid;
+    if (!range) {
+      t += s;  // < 2^50 + 2^32: no overflow
+      if (per && t >= (kMaxCallBytes + per - 1) / per) range = true;
+      else off.push_back(t);
+    }
+  }
+  if (range) {
+    off.clear();
+    return kRange;
+  }
+  return kOk;
+}
+
+struct Range {
+  size_t b0, b1;  // blocks [b0, b1)
+};
+
+// Launch spans: consecutive block ranges that cover every block once, cut on
+// block boundaries only, each of at most tile_limit tiles and kMaxSpanBlocks
+// blocks.  A block of more tiles than the limit gets a span of its own.
+inline std::vector<Range> cut_spans(const size_t* sizes, size_t n, uint64_t tile_limit,
+                                    uint64_t block_limit = kMaxSpanBlocks) {
+  std::vector<Range> out;
+  size_t b0 = 0;
+  uint64_t cols = 0;
+  for (size_t b = 0; b < n; ++b) {
+    const uint64_t c = (uint64_t)sizes[b] / 16;
+    const uint64_t tiles = (cols + c + kTileCols - 1) / kTileCols;
+    if (b > b0 && (tiles > tile_limit || b - b0 >= block_limit)) {
+      out.push_back({b0, b});
+      b0 = b;
+      cols = 0;
+    }
+    cols += c;
+  }
+  if (n > b0) out.push_back({b0, n});
+  return out;
+}
+
+// Pipeline waves: consecutive block ranges that cover every block once, cut
+// on block boundaries only, each of at most byte_limit bytes where block b
+// weighs per * S[b].  A block heavier than the limit gets a wave of its own.
+inline std::vector<Range> cut_waves(const size_t* sizes, size_t n, uint64_t per,
+                                    uint64_t byte_limit) {
+  std::vector<Range> out;
+  size_t b0 = 0;
+  uint64_t bytes = 0;
+  for (size_t b = 0; b < n; ++b) {
+    const uint64_t w = per * (uint64_t)sizes[b];
+    if (b > b0 && bytes + w > byte_limit) {
+      out.push_back({b0, b});
+      b0 = b;
+      bytes = 0;
+    }
+    bytes += w;
+  }
+  if (n > b0) out.push_back({b0, n});
+  return out;
+}
+
+// One tile of the column space.  The index leaves zero-size blocks out:
+// q numbers the non-empty blocks of the span, orig[q] is the caller's block
+// (relative to the span's first), coff[q] its first column and coff[nq] the
+// span's column count.
+struct TileDesc {
+  uint32_t q_first;  // non-empty block holding the tile's first column
+  uint32_t nblk;     // non-empty blocks the tile's columns touch (1..64); 1: inside one block
+  uint32_t c0;       // the tile's first column, inside block q_first
+  uint32_t cols;     // columns of block q_first (S / 16)
+};
+static_assert(sizeof(TileDesc) == 16, "read as one 16-byte load");
+
+struct Counts {
+  uint64_t nq = 0, cols = 0, tiles = 0;
+};
+inline Counts index_counts(const size_t* sizes, size_t n) {
+  Counts c;
+  for (size_t b = 0; b < n; ++b)
+    if (sizes[b]) {
+      ++c.nq;
+      c.cols += (uint64_t)sizes[b] / 16;
+    }
+  c.tiles = (c.cols + kTileCols - 1) / kTileCols;
+  return c;
+}
+
+// Fills coff[nq + 1], orig[nq] and desc[tiles] (index_counts' figures) of
+// the span `sizes[0..n)`.
+inline void build_index(const size_t* sizes, size_t n, uint64_t* coff, uint32_t* orig,
+                        TileDesc* desc) {
+  uint64_t nq = 0, cols = 0;
+  for (size_t b = 0; b < n; ++b)
+    if (sizes[b]) {
+      orig[nq] = (uint32_t)b;
+      coff[nq++] = cols;
+      cols += (uint64_t)sizes[b] / 16;
+    }
+  coff[nq] = cols;
+  const uint64_t tiles = (cols + kTileCols - 1) / kTileCols;
+  uint64_t q = 0;
+  for (uint64_t t = 0; t < tiles; ++t) {
+    const uint64_t c = t * kTileCols;
+    const uint64_t end = c + kTileCols < cols ? c + kTileCols : cols;
+    while (coff[q + 1] <= c) ++q;
+    uint64_t qe = q;
+    while (coff[qe + 1] < end) ++qe;
+    TileDesc& d = desc[t];
+    d.q_first = (uint32_t)q;
+    d.nblk = (uint32_t)(qe - q + 1);
+    d.c0 = (uint32_t)(c - coff[q]);
+    d.cols = (uint32_t)(coff[q + 1] - coff[q]);
+  }
+}
+
+struct Index {
+  std::vector<uint64_t> coff;
+  std::vector<uint32_t> orig;
+  std::vector<TileDesc> desc;
+};
+inline Index build_index(const size_t* sizes, size_t n) {
+  const Counts c = index_counts(sizes, n);
+  Index ix;
+  ix.coff.resize(c.nq + 1);
+  ix.orig.resize(c.nq);
+  ix.desc.resize(c.tiles);
+  build_index(sizes, n, ix.coff.data(), ix.orig.data(), ix.desc.data());
+  return ix;
+}
+
+}  // namespace ragged
+}  // namespace memo_ec

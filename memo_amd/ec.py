@@ -63,6 +63,7 @@ PROBE_MODES = {"copy": 0, "read": 1, "write": 2}  # memo_ec_probe_mode
 _ROOT = os.path.dirname(_HERE)
 BUILD_SOURCES = [os.path.join(_ROOT, "include", "memo_ec.h"),
                  os.path.join(_HERE, "csrc", "ec_kernels.h"),
+                 os.path.join(_HERE, "csrc", "ragged_plan.h"),
                  os.path.join(_HERE, "csrc", "ec_kernels.hip"),
                  os.path.join(_HERE, "csrc", "memo_ec.cpp")]
 
@@ -79,6 +80,7 @@ EXPORTS = [
     "memo_ec_version", "memo_ec_device_count", "memo_ec_rebuild_segments",
     "memo_ec_ctx_set_option", "memo_ec_ctx_get_option", "memo_ec_build_id",
     "memo_ec_device_identity", "memo_ec_stream_probe", "memo_ec_verify_batch",
+    "memo_ec_encode_ragged", "memo_ec_verify_ragged",
 ]
 
 # memo_ec_verify_batch verdict words: MEMO_EC_VERDICT_UNLOCATED of the header.
@@ -145,6 +147,11 @@ def _lib():
         L.memo_ec_stream_probe.argtypes = [ctypes.c_void_p, c_int, c_int, _sz, _sz, _u8p, _u8p, c_int]
         L.memo_ec_verify_batch.argtypes = [ctypes.c_void_p, c_int, c_int, _sz, _sz, _u8p, _u8p,
                                            ctypes.c_void_p, c_int]
+        if hasattr(L, "memo_ec_encode_ragged"):  # absent from older builds (MEMO_EC_LIB A/B runs)
+            L.memo_ec_encode_ragged.argtypes = [ctypes.c_void_p, c_int, c_int, _sz, ctypes.c_void_p,
+                                                _u8p, _u8p, c_int]
+            L.memo_ec_verify_ragged.argtypes = [ctypes.c_void_p, c_int, c_int, _sz, ctypes.c_void_p,
+                                                _u8p, _u8p, ctypes.c_void_p, c_int]
         _LIB = L
     return _LIB
 
@@ -409,6 +416,52 @@ class Codec:
         _check(_lib().memo_ec_verify_batch(self._ctx, k, m, S, n, dp, pp, vp, where), "verify")
         return verdict
 
+    def encode_ragged(self, k, m, sizes, data, parity):
+        """memo_ec_encode_ragged: blocks of their own shard sizes (sizes[b],
+        multiples of 64; 0 allowed) packed back to back with no padding.  data
+        holds k * T and parity m * T bytes, T = sum(sizes): shard j of block b
+        at k * off[b] + j * sizes[b] (ragged_offsets).  Flat uint8 buffers;
+        device (async) or host (sync)."""
+        sz = _sizes(sizes)
+        dp, dw = _ptr(data)
+        pp, pw = _ptr(parity)
+        if (dw == DEVICE) != (pw == DEVICE):
+            raise ValueError("data and parity must both be device or both host buffers")
+        _check_ragged_len(sz, ((data, k, "data"), (parity, m, "parity")))
+        where = DEVICE if dw == DEVICE else (HOST_PINNED if dw == pw == HOST_PINNED else HOST)
+        _check(_lib().memo_ec_encode_ragged(self._ctx, k, m, len(sz), sz.ctypes.data, dp, pp, where),
+               "encode_ragged")
+        return parity
+
+    def verify_ragged(self, k, m, sizes, data, parity, verdict=None):
+        """memo_ec_verify_ragged: Codec.verify over the layout of
+        encode_ragged; verdict has len(sizes) words (made when None), 0 for a
+        zero-size block."""
+        sz = _sizes(sizes)
+        n = len(sz)
+        dp, dw = _ptr(data)
+        pp, pw = _ptr(parity)
+        if (dw == DEVICE) != (pw == DEVICE):
+            raise ValueError("data and parity must both be device or both host buffers")
+        _check_ragged_len(sz, ((data, k, "data"), (parity, m, "parity")))
+        if verdict is None:
+            # as in verify(): the library zeroes the words on the ctx stream
+            written = m > 0 and n > 0 and int(sz.sum()) > 0
+            if _is_torch(data):
+                import torch
+                make = torch.empty if written else torch.zeros
+                verdict = make(n, dtype=torch.int32, device=data.device,
+                               pin_memory=(dw == pw == HOST_PINNED))
+            else:
+                verdict = (np.empty if written else np.zeros)(n, dtype=np.uint32)
+        vp, vw = _ptr_words(verdict, n)
+        if (vw == DEVICE) != (dw == DEVICE):
+            raise ValueError("verdict must live where the shards do (device or host)")
+        where = DEVICE if dw == DEVICE else (HOST_PINNED if dw == pw == vw == HOST_PINNED else HOST)
+        _check(_lib().memo_ec_verify_ragged(self._ctx, k, m, n, sz.ctypes.data, dp, pp, vp, where),
+               "verify_ragged")
+        return verdict
+
     def rebuild(self, k, m, surv_idx, surv, lost_idx, out, S=None, n=None):
         """out (n x e x S) <- the k survivor shards surv (n x k x S) of each block."""
         sp, sw = _ptr(surv)
@@ -542,6 +595,34 @@ def mac_kchunk(k, R):
     if k in (6, 12, 14):
         return k if R <= 4 else 4
     return 4
+
+
+def _sizes(sizes):
+    """The host size_t array memo_ec_*_ragged reads."""
+    a = np.asarray(sizes)
+    if a.size and (a.dtype.kind not in "iu" or (a < 0).any()):
+        raise ValueError("sizes must be non-negative integers")
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.uint64)
+
+
+def ragged_offsets(sizes):
+    """off[0..n] of a ragged batch: off[b] = sizes[0] + ... + sizes[b-1]
+    (uint64).  Data shard j of block b starts at k * off[b] + j * sizes[b],
+    parity shard i at m * off[b] + i * sizes[b]; off[n] = T."""
+    sz = _sizes(sizes)
+    off = np.zeros(len(sz) + 1, dtype=np.uint64)
+    np.cumsum(sz, out=off[1:])
+    return off
+
+
+def _check_ragged_len(sz, bufs):
+    """Each buffer holds its k (or m) * T bytes: the C side takes the
+    sizes' word for it."""
+    T = int(sz.sum())
+    for buf, per, name in bufs:
+        have = buf.numel() if _is_torch(buf) else buf.size
+        if have < per * T:
+            raise ValueError("%s holds %d bytes, the sizes need %d" % (name, have, per * T))
 
 
 def _check_pattern(si, li, k, m):
