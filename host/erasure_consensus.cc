@@ -107,6 +107,47 @@ std::vector<RebuildBatch> plan_rebuild_batches(const std::vector<RebuildItem>& i
   return batches;
 }
 
+bool mixed_sizes(const std::vector<RebuildItem>& items, const RebuildBatch* bs, size_t nx) {
+  for (size_t x = 0; x < nx; ++x)
+    for (size_t i : bs[x].items)
+      if (items[i].S != items[bs[0].items[0]].S) return true;
+  return false;
+}
+
+std::vector<RaggedRebuildGroup> group_ragged_rebuilds(const std::vector<RebuildItem>& items,
+                                                      const RebuildBatch* bs, size_t nx, int k) {
+  std::vector<RaggedRebuildGroup> gs;
+  for (size_t x = 0; x < nx; ++x) {
+    const RebuildBatch& b = bs[x];
+    size_t at = 0;
+    while (at < gs.size() &&
+           !(gs[at].e == b.e && gs[at].uniform == b.uniform && (!b.uniform || gs[at].pat == b.pat)))
+      ++at;
+    if (at == gs.size()) {
+      RaggedRebuildGroup g;
+      g.e = b.e;
+      g.uniform = b.uniform;
+      if (b.uniform) {
+        g.pat = b.pat;
+        g.sidx.assign(b.pat.begin(), b.pat.begin() + k);
+        g.lidx.assign(b.pat.begin() + k, b.pat.end());
+      }
+      gs.push_back(std::move(g));
+    }
+    RaggedRebuildGroup& g = gs[at];
+    for (size_t i : b.items) {
+      g.items.push_back(i);
+      g.sizes.push_back(items[i].S);
+      g.off.push_back(g.off.back() + items[i].S);
+      if (!b.uniform) {
+        g.sidx.insert(g.sidx.end(), items[i].pat, items[i].pat + k);
+        g.lidx.insert(g.lidx.end(), items[i].pat + k, items[i].pat + k + b.e);
+      }
+    }
+  }
+  return gs;
+}
+
 std::vector<size_t> cut_rebuild_chunks(const std::vector<RebuildBatch>& batches, int k, size_t limit) {
   std::vector<size_t> cuts{0};
   size_t acc = 0;
@@ -298,6 +339,22 @@ void Codec::rebuild(int k, int m, size_t S, size_t n, const uint8_t* surv_idx,
     return rc;
   }, "rebuild");
   ++rebuild_calls_;
+}
+
+void Codec::rebuild_ragged(int k, int m, size_t n, const size_t* sizes, const uint8_t* surv_idx,
+                           const uint8_t* surv, const uint8_t* lost_idx, int e, bool uniform,
+                           uint8_t* out, bool pinned) {
+  split_ragged(n, sizes, [&](size_t d, size_t b0, size_t cnt, size_t off) {
+    auto* c = acquire(d);
+    const int rc = memo_ec_rebuild_ragged(c, k, m, cnt, sizes + b0, uniform ? surv_idx : surv_idx + b0 * k,
+                                          surv + off * k, uniform ? lost_idx : lost_idx + b0 * e, e,
+                                          uniform ? 1 : 0, out + off * e,
+                                          pinned ? MEMO_EC_HOST_PINNED : MEMO_EC_HOST);
+    release(d, c);
+    return rc;
+  }, "rebuild_ragged");
+  ++(uniform ? uniform_calls_ : rebuild_calls_);
+  ++ragged_calls_;
 }
 
 void Codec::rebuild_uniform(int k, int m, size_t S, size_t n, const uint8_t* surv_idx,
@@ -1809,9 +1866,15 @@ size_t ErasureConsensus::stage_rebuilds(const std::vector<RebuildItem>& items,
                                         const Rebuilt& rebuilt, const char* rebuilt_lap, PhaseTimer& tm) {
   const int k = o_.k, m = o_.m;
   const std::vector<size_t> cuts = cut_rebuild_chunks(batches, k, limit);
+  size_t calls = 0;
   for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
     const size_t nx = cuts[ci + 1] - cuts[ci];
     const RebuildBatch* bs = batches.data() + cuts[ci];
+    if (o_.ragged_rebuild && mixed_sizes(items, bs, nx)) {
+      calls += stage_rebuilds_ragged(items, bs, nx, survivors, staged, rebuilt, rebuilt_lap, tm);
+      continue;
+    }
+    ++calls;
     std::vector<size_t> o_surv(nx), o_out(nx);             // each batch's part of the two leases
     std::vector<std::vector<uint8_t>> sidx(nx), lidx(nx);  // per-block patterns (no uniform batch's)
     std::vector<std::pair<size_t, size_t>> work;  // (batch, block) pairs for the pool
@@ -1875,7 +1938,58 @@ size_t ErasureConsensus::stage_rebuilds(const std::vector<RebuildItem>& items,
     });
     tm.lap(rebuilt_lap);
   }
-  return cuts.size() - 1;
+  return calls;
+}
+
+// One staged chunk with "ragged-rebuild": the chunk's batches regrouped by
+// what one memo_ec_rebuild_ragged call can take -- every per-block-pattern
+// item of one e, and every item of one shared pattern -- each group packed at
+// its blocks' own shard sizes into its part of the two leases.
+size_t ErasureConsensus::stage_rebuilds_ragged(const std::vector<RebuildItem>& items, const RebuildBatch* bs,
+                                               size_t nx, const Survivors& survivors,
+                                               const std::function<void(size_t)>& staged,
+                                               const Rebuilt& rebuilt, const char* rebuilt_lap,
+                                               PhaseTimer& tm) {
+  const int k = o_.k, m = o_.m;
+  std::vector<RaggedRebuildGroup> gs = group_ragged_rebuilds(items, bs, nx, k);
+  std::vector<std::pair<size_t, size_t>> work;  // (group, block) pairs for the pool
+  size_t surv_bytes = 0, out_bytes = 0;
+  for (size_t x = 0; x < gs.size(); ++x) {
+    RaggedRebuildGroup& g = gs[x];
+    g.o_surv = surv_bytes;
+    g.o_out = out_bytes;
+    surv_bytes += (size_t)k * g.off.back();
+    out_bytes += (size_t)g.e * g.off.back();
+    for (size_t bi = 0; bi < g.items.size(); ++bi) work.emplace_back(x, bi);
+  }
+  PinnedArena::Lease surv_all = arena_.lease(surv_bytes), out_all = arena_.lease(out_bytes);
+  ragged_rebuild_staged_ += surv_bytes;
+  tm.lap("alloc");
+  pool_.parallel_for(work.size(), [&](size_t t) {
+    const RaggedRebuildGroup& g = gs[work[t].first];
+    const size_t bi = work[t].second, S = g.sizes[bi];
+    const uint8_t* src[MEMO_EC_MAX_K];
+    survivors(g.items[bi], src);
+    uint8_t* at = surv_all.data() + g.o_surv + (size_t)k * g.off[bi];
+    for (int s = 0; s < k; ++s) std::memcpy(at + (size_t)s * S, src[s], S);
+  });
+  tm.lap("copy_in");
+  if (staged) {
+    pool_.parallel_for(work.size(), [&](size_t t) { staged(gs[work[t].first].items[work[t].second]); });
+    tm.lap("free");
+  }
+  const bool pinned = surv_all.pinned() && out_all.pinned();
+  for (const RaggedRebuildGroup& g : gs)
+    codec_.rebuild_ragged(k, m, g.items.size(), g.sizes.data(), g.sidx.data(), surv_all.data() + g.o_surv,
+                          g.lidx.data(), g.e, g.uniform, out_all.data() + g.o_out, pinned);
+  tm.lap("rebuild");
+  pool_.parallel_for(work.size(), [&](size_t t) {
+    const RaggedRebuildGroup& g = gs[work[t].first];
+    const size_t bi = work[t].second;
+    rebuilt(g.items[bi], out_all.data() + g.o_out + (size_t)g.e * g.off[bi], g.sizes[bi]);
+  });
+  tm.lap(rebuilt_lap);
+  return gs.size();
 }
 
 void ErasureConsensus::_resign() { backend_->resign(); }
@@ -2665,7 +2779,8 @@ void ErasureConsensus::membership_loop() {
 // "erasure" configuration: {"type": "erasure", "data-shards": k,
 // "parity-shards": m, "backend-replication-factor": f, and optionally
 // "device", "batch-max", "eviction-delay" (s), "stage-mb", "threads",
-// "fetch-hedge", "verify-subsets", "ragged-store" (0 / 1)};
+// "fetch-hedge", "verify-subsets", "ragged-store" (0 / 1),
+// "ragged-rebuild" (0 / 1)};
 // kebab-case keys as "replication-factor" (Paxos.cc:2273-2276).
 namespace {
 struct RegisterErasure {
@@ -2686,6 +2801,7 @@ struct RegisterErasure {
       o.fetch_hedge = get("fetch-hedge", o.fetch_hedge);
       o.verify_subsets = get("verify-subsets", o.verify_subsets);
       o.ragged_store = get("ragged-store", o.ragged_store ? 1 : 0) != 0;
+      o.ragged_rebuild = get("ragged-rebuild", o.ragged_rebuild ? 1 : 0) != 0;
       if (o.batch_max < 1 || stage_mb < 1 || o.threads < 1)
         throw Error("erasure: batch-max, stage-mb and threads must be positive");
       if (o.fetch_hedge < 0 || o.verify_subsets < 0)

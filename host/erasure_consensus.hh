@@ -71,6 +71,14 @@ class Codec {
                      const uint8_t* parity, uint32_t* verdict, bool pinned = false);
   void rebuild(int k, int m, size_t S, size_t n, const uint8_t* surv_idx, const uint8_t* surv,
                const uint8_t* lost_idx, int e, uint8_t* out, bool pinned = false);
+  // The rebuild of a ragged batch (memo_ec_rebuild_ragged): survivor t of
+  // block b at surv + k * off[b] + t * sizes[b], rebuilt shard r at out +
+  // e * off[b] + r * sizes[b]; surv_idx n x k and lost_idx n x e, or (uniform)
+  // one pattern of k and e entries for every block.  Cut over the devices on
+  // block boundaries by bytes, like the other ragged calls.
+  void rebuild_ragged(int k, int m, size_t n, const size_t* sizes, const uint8_t* surv_idx,
+                      const uint8_t* surv, const uint8_t* lost_idx, int e, bool uniform, uint8_t* out,
+                      bool pinned = false);
   // One erasure pattern for all n blocks (memo_ec_rebuild_uniform):
   // surv_idx has k entries, lost_idx e.
   void rebuild_uniform(int k, int m, size_t S, size_t n, const uint8_t* surv_idx,
@@ -82,8 +90,10 @@ class Codec {
   void rebuild_segments(const std::vector<memo_ec_rebuild_segment>& segs, bool pinned = false);
   uint64_t encode_calls() const { return encode_calls_; }
   uint64_t verify_calls() const { return verify_calls_; }
-  // encode_ragged and verify_ragged calls (a ragged encode also counts in
-  // encode_calls(), a ragged verify in verify_calls())
+  // encode_ragged, verify_ragged and rebuild_ragged calls (a ragged encode
+  // also counts in encode_calls(), a ragged verify in verify_calls(), a
+  // ragged rebuild in rebuild_calls() or, with a shared pattern,
+  // uniform_calls())
   uint64_t ragged_calls() const { return ragged_calls_; }
   uint64_t rebuild_calls() const { return rebuild_calls_; }
   uint64_t uniform_calls() const { return uniform_calls_; }
@@ -237,6 +247,25 @@ std::vector<RebuildBatch> plan_rebuild_batches(const std::vector<RebuildItem>& i
 // no chunk for no batches.
 constexpr size_t kNoStageLimit = ~(size_t)0;
 std::vector<size_t> cut_rebuild_chunks(const std::vector<RebuildBatch>& batches, int k, size_t limit);
+// With "ragged-rebuild": the batches [bs, bs + nx) of one staged chunk
+// regrouped into what one Codec::rebuild_ragged call takes -- every
+// per-block-pattern item of one e (in batch order), and every item of one
+// shared pattern -- with each group's shard sizes and byte offsets.
+struct RaggedRebuildGroup {
+  int e = 0;
+  bool uniform = false;
+  std::vector<uint8_t> pat;         // uniform: survivors (k) || lost (e)
+  std::vector<size_t> items;        // members, as positions in the planner's input
+  std::vector<size_t> sizes;        // their shard sizes
+  std::vector<size_t> off{0};       // off[b] = sizes[0] + ... + sizes[b-1]; off[n] = T
+  std::vector<uint8_t> sidx, lidx;  // n x k / n x e, or (uniform) k / e entries
+  size_t o_surv = 0, o_out = 0;     // the group's part of the chunk's two leases
+};
+// Whether the chunk's items have more than one shard size (a chunk of one
+// size makes the rebuild_segments call it made before, key on or off).
+bool mixed_sizes(const std::vector<RebuildItem>& items, const RebuildBatch* bs, size_t nx);
+std::vector<RaggedRebuildGroup> group_ragged_rebuilds(const std::vector<RebuildItem>& items,
+                                                      const RebuildBatch* bs, size_t nx, int k);
 
 // ---------------------------------------------------------- shard format
 // On-wire / on-silo shard: a 128-byte header + S payload bytes.  The header
@@ -404,6 +433,15 @@ struct ErasureOptions {
   // host/tests/test_erasure.cc store_many_stages_in_chunks asks for at least
   // 5 encode calls of a request that stages 4 chunks.
   bool ragged_store = false;
+  // "ragged-rebuild": a staged chunk of the multi-fetch or the repair that
+  // holds more than one shard size makes
+  // ONE ragged rebuild call per erasure count e for its per-block-pattern
+  // blocks and one per shared pattern, every survivor staged at its own shard
+  // size with no padding byte; off: one rebuild_segments call whose segments
+  // are power-of-two size buckets padded to their largest shard.  Off by
+  // default for the reason ragged_store is: host/tests/test_erasure.cc
+  // counts the codec's calls.
+  bool ragged_rebuild = false;
 };
 
 // The peer ErasureConsensus::make_local makes, in front of its backend's
@@ -518,6 +556,9 @@ class ErasureConsensus : public StackedConsensus {
   const Codec& codec() const { return codec_; }
   uint64_t arena_leases() const { return arena_.leases(); }
   uint64_t arena_leased_bytes() const { return arena_.leased_bytes(); }
+  // survivor bytes staged by "ragged-rebuild" chunks so far: k * sum(S) of
+  // the blocks they rebuilt, no padding (tests)
+  uint64_t ragged_rebuild_staged() const { return ragged_rebuild_staged_.load(); }
   // bytes of the data (not parity) leases the store path staged so far
   uint64_t store_data_bytes() const { return store_data_bytes_.load(); }
   size_t arena_kept_bytes() const { return arena_.kept_bytes(); }
@@ -640,12 +681,20 @@ class ErasureConsensus : public StackedConsensus {
   // payloads (items[i].S bytes each); staged(i), if any, runs once they are
   // copied in, before the codec call; rebuilt(i, shards, stride) gets lost
   // shard r at shards + r * stride (that pass's timing lap: rebuilt_lap).
-  // Returns the codec calls made.
+  // Returns the codec calls made: one per chunk, or what
+  // stage_rebuilds_ragged made of it.  With ragged_rebuild the chunk's batches
+  // are regrouped when they hold several shard sizes (stage_rebuilds_ragged,
+  // which returns its codec calls): one ragged call per e and one per
+  // shared pattern, leases of exactly k * sum(S) and e * sum(S) bytes, stride
+  // items[i].S.
   using Survivors = std::function<void(size_t, const uint8_t**)>;
   using Rebuilt = std::function<void(size_t, const uint8_t*, size_t)>;
   size_t stage_rebuilds(const std::vector<RebuildItem>& items, const std::vector<RebuildBatch>& batches,
                         size_t limit, const Survivors& survivors, const std::function<void(size_t)>& staged,
                         const Rebuilt& rebuilt, const char* rebuilt_lap, PhaseTimer& tm);
+  size_t stage_rebuilds_ragged(const std::vector<RebuildItem>& items, const RebuildBatch* bs, size_t nx,
+                             const Survivors& survivors, const std::function<void(size_t)>& staged,
+                             const Rebuilt& rebuilt, const char* rebuilt_lap, PhaseTimer& tm);
   // One shard-size bucket of blocks encoded: their shards zero-padded into
   // S-byte slots (S the largest) of two leases, copied in on the pool or
   // serially, then one encode call.
@@ -756,6 +805,7 @@ class ErasureConsensus : public StackedConsensus {
   // stored again after its removal).
   bool held_elsewhere(const Address& a, const Address& except) const;
   std::map<Address, std::vector<OwedRemove>> pending_rm_;  // node -> removals still owed
+  std::atomic<uint64_t> ragged_rebuild_staged_{0};
   // in-flight fetches from this client per node (the reference's
   // Paxos::_transfers), hashed into per-thread-slot counters: every shard
   // fetch adds and subtracts, only a degraded fetch's ordering reads them

@@ -358,6 +358,45 @@ int memo_ec_encode_segments(memo_ec_ctx *ctx, int nseg,
 int memo_ec_rebuild_segments(memo_ec_ctx *ctx, int nseg,
                              const memo_ec_rebuild_segment *segs, int where);
 
+/* Ragged rebuild: n blocks, each with its own shard size, rebuilt in one call
+ * with no padding byte.  sizes, off[b] and T are those of
+ * memo_ec_encode_ragged (host array, validated before anything is enqueued
+ * with the same MEMO_EC_EINVAL / MEMO_EC_ERANGE rules):
+ *   surv holds k * T bytes; survivor t of block b, in surv_idx order, is at
+ *        surv + k * off[b] + t * S[b];
+ *   out  holds e * T bytes; rebuilt shard r, in lost_idx order, is at
+ *        out + e * off[b] + r * S[b].
+ * With every S[b] equal this is byte for byte the layout, and the output, of
+ * memo_ec_rebuild_batch (uniform != 0: memo_ec_rebuild_uniform).
+ *
+ * One e serves the call, 0 <= e <= m; e == 0, n == 0 or T == 0 writes
+ * nothing.
+ * uniform == 0: surv_idx is n x k and lost_idx n x e bytes in the memory
+ *   `where` names, at any byte alignment.  Every block's pattern is
+ *   validated, zero-size blocks included; an invalid one gives a block whose
+ *   `out` bytes are all zero while the others are still rebuilt, and
+ *   MEMO_EC_ESINGULAR once: at memo_ec_synchronize for MEMO_EC_DEVICE, from
+ *   the call itself for host memory.
+ * uniform != 0: surv_idx is k and lost_idx e bytes in HOST memory whatever
+ *   `where` says; an invalid pattern returns MEMO_EC_ESINGULAR before
+ *   anything is enqueued.  Tables come from the ctx's pattern cache, as for
+ *   memo_ec_rebuild_uniform.
+ *
+ * surv and out are 16-byte aligned in MEMO_EC_DEVICE / MEMO_EC_HOST_PINNED
+ * memory (MEMO_EC_EINVAL otherwise, before anything is enqueued); pageable
+ * buffers may sit at any byte address.  MEMO_EC_DEVICE calls are asynchronous
+ * on the ctx stream and need no synchronize between them; host calls up to
+ * MEMO_EC_OPT_ZERO_COPY_BYTES run zero-copy, larger ones through the copy
+ * pipeline in waves cut on block boundaries.  Per-block patterns always run
+ * the decode rows and then the rows multiply-accumulate over ragged tiles
+ * (gf_mac_ragged_rows_kernel): MEMO_EC_OPT_REBUILD_PATH and the
+ * MEMO_EC_OPT_IMAGE_* options do not apply to this call.  Like the other
+ * ragged calls it cannot be captured into a HIP graph. */
+int memo_ec_rebuild_ragged(memo_ec_ctx *ctx, int k, int m, size_t n, const size_t *sizes,
+                           const uint8_t *surv_idx, const uint8_t *surv,
+                           const uint8_t *lost_idx, int e, int uniform,
+                           uint8_t *out, int where);
+
 /* Batched SHA-256 (FIPS 180-4): digest_i = SHA-256(prefix_i || msg_i) for
  * i < n, with prefix_i = prefix + i*prefix_stride (prefix_len bytes; 0 for
  * none) and msg_i = msg + i*msg_stride of msg_len[i] bytes (msg_len == NULL:

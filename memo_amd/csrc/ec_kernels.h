@@ -204,6 +204,12 @@ hipError_t launch_verify_locate(const LocateArgs& a, hipStream_t st);
 // gf_mac_ragged_kernel (verify false) / gf_verify_ragged_kernel over one span.
 hipError_t launch_mac_ragged(int KC, int R, bool verify, const RaggedLaunch& L, uint32_t grid,
                              size_t lds, hipStream_t st);
+// gf_mac_ragged_rows_kernel over one span of the capped tiles (ragged::
+// build_rows_index: L.idx.desc holds two uint4 per tile); of `seg` it also
+// reads coef (the span's first block's decode rows), coef_bstride, coef_rows
+// and lo_dw.
+hipError_t launch_mac_ragged_rows(int KC, int R, const RaggedLaunch& L, uint32_t grid, size_t lds,
+                                  hipStream_t st);
 hipError_t launch_verify_locate_ragged(const RaggedLocateArgs& a, hipStream_t st);
 hipError_t launch_fill(const FillArgs& a, hipStream_t st);
 hipError_t launch_sha256(const Sha256Args& a, hipStream_t st);

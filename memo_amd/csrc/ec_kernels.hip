@@ -349,6 +349,64 @@ __device__ __forceinline__ Unit locate_ragged(const MacSeg& sg, const RaggedIdx&
   return u;
 }
 
+// Ragged locate of the per-block-pattern rebuild (gf_mac_ragged_rows_kernel):
+// locate_ragged over the capped tiles of ragged::build_rows_index.  Every
+// non-empty block of the tile has its own table set (nsets = nblk, set s =
+// block q_first + s), the tile starts at the descriptor's column instead of
+// 256 * tile, and it may end early, on the start of block q_first + nblk:
+// entry nblk - 1 of the walk is then the tile's end, so the lanes behind it
+// count nblk starts at or before them and are idle like the lanes past the
+// span's columns.  ov: the caller's block number of q_first + (lane % 64),
+// clamped to the tile's blocks (load_coefs_ragged addresses the rows by it).
+__device__ __forceinline__ Unit locate_ragged_rows(const MacSeg& sg, const RaggedIdx& rg,
+                                                   uint64_t tile, uint32_t& ov) {
+  Unit u;
+  const uint32_t tid = threadIdx.x, lane = tid % 64;
+  const uint4 d = rg.desc[2 * tile], d2 = rg.desc[2 * tile + 1];
+  const uint32_t q_first = __builtin_amdgcn_readfirstlane(d.x);
+  const uint32_t nblk = __builtin_amdgcn_readfirstlane(d.y);
+  const uint32_t c0 = __builtin_amdgcn_readfirstlane(d.z);
+  const uint32_t c_first = __builtin_amdgcn_readfirstlane(d.w);
+  const uint64_t base = ((uint64_t)__builtin_amdgcn_readfirstlane(d2.y) << 32) |
+                        __builtin_amdgcn_readfirstlane(d2.x);
+  const uint32_t ncols = __builtin_amdgcn_readfirstlane(d2.z);
+  ov = rg.orig[(uint64_t)q_first + (lane < nblk ? lane : nblk - 1u)];
+  int32_t start = -(int32_t)c0;
+  int32_t end = (int32_t)(c_first - c0);
+  uint32_t cnt = 0;
+  if (nblk == 1) {
+    u.valid = tid < ncols;
+  } else {
+    int32_t e = 0x7fffffff;
+    if (lane < nblk) e = (int32_t)(uint32_t)(rg.coff[(uint64_t)q_first + 1 + lane] - base);
+    const int32_t first_end = __builtin_amdgcn_readlane(e, 0);
+    end = 0x7fffffff;
+    for (uint32_t j = 0; j < nblk; ++j) {
+      const int32_t r = __builtin_amdgcn_readlane(e, j);
+      const bool take = r <= (int32_t)tid;
+      start = take ? r : start;
+      cnt += take ? 1u : 0u;
+      end = take ? end : (r < end ? r : end);
+    }
+    u.valid = cnt < nblk;
+    if (!u.valid) {
+      cnt = 0;
+      start = -(int32_t)c0;
+      end = first_end;
+    }
+  }
+  const uint32_t t = u.valid ? tid : 0u;
+  const uint32_t cc = (uint32_t)((int32_t)t - start);  // column inside the block
+  u.rs = (uint32_t)(end - start) * 16u;                 // < 2^32
+  u.b_first = q_first;
+  u.nsets = nblk;
+  u.set = cnt;
+  const uint64_t bcol = (uint64_t)((int64_t)base + start);
+  u.pin = sg.in + bcol * (16ull * sg.kin) + (uint64_t)cc * 16;
+  u.pout = sg.out + bcol * (16ull * sg.r) + (uint64_t)cc * 16;
+  return u;
+}
+
 // Copy nsets table images (set s = block b_first + s) into LDS.
 __device__ __forceinline__ void stage_tables(const MacSeg& sg, const Unit& u, uint32_t set_dw,
                                              uint32_t* s_tab) {
@@ -535,6 +593,31 @@ __device__ __forceinline__ void load_coefs(const MacSeg& sg, const Unit& u,
     }
   }
 }
+// load_coefs of the ragged rebuild.  The index leaves zero-size blocks out,
+// so set s of the tile is the caller's block orig[q_first + s] and its rows
+// are at coef + that * coef_bstride: no contiguous range.  `ov` holds that
+// block number for set (lane % 64) in every wave (locate_ragged_rows; a tile
+// has at most 64 sets), so a slot's comes by one cross-lane read and the
+// loads stay unconditional, one memory latency behind the descriptor.
+// Padding slots and slots past the tile's sets load the rows' first byte.
+template <int R, int KP>
+__device__ __forceinline__ void load_coefs_ragged(const MacSeg& sg, const Unit& u, uint32_t ov,
+                                                  uint32_t (&cv)[MAC_COEF_REGS]) {
+  const uint32_t total = u.nsets * (R * KP);
+  const uint32_t tid = threadIdx.x;
+#pragma unroll
+  for (int q = 0; q < MAC_COEF_REGS; ++q) {
+    const uint32_t ci = tid + 256u * q;
+    const uint32_t set = ci / (R * KP), rem = ci - set * (R * KP);
+    const uint32_t i = rem / KP, j = rem - i * KP;
+    const uint32_t blk = (uint32_t)__shfl((int)ov, (int)(set & 63u), 64);
+    const uint64_t off = coef_slot_ok<R, KP>(sg, ci, total)
+                             ? (uint64_t)blk * sg.coef_bstride + i * sg.kin + j
+                             : 0u;
+    cv[q] = sg.coef[off];
+  }
+}
+
 template <int R, int KP>
 __device__ __forceinline__ void store_images(const MacSeg& sg, const Unit& u,
                                              const uint32_t (&cv0)[MAC_COEF_REGS], uint32_t* s_tab) {
@@ -572,6 +655,26 @@ __device__ __forceinline__ void stage_images(const MacSeg& sg, const Unit& u, ui
     uint4 q;
     uint32_t lo;
     coef_image(coef_at<R>(sg, u, ci, sg.kpad), q, lo);
+    put_image(s_tab, sg, per, ci, q, lo);
+  }
+}
+
+// stage_images of the ragged rebuild: set s's rows are the caller's block
+// orig[q_first + s]'s.
+template <int R>
+__device__ __forceinline__ void stage_images_ragged(const MacSeg& sg, const Unit& u,
+                                                    const RaggedIdx& rg, uint32_t* s_tab) {
+  const uint32_t kpad = sg.kpad, per = R * kpad;
+  const uint32_t total = u.nsets * per;
+  for (uint32_t ci = threadIdx.x; ci < total; ci += 256) {
+    const uint32_t set = ci / per, rem = ci - set * per;
+    const uint32_t i = rem / kpad, j = rem - i * kpad;
+    uint32_t c = 0;
+    if (i < sg.coef_rows && j < sg.kin)
+      c = sg.coef[(uint64_t)rg.orig[u.b_first + set] * sg.coef_bstride + i * sg.kin + j];
+    uint4 q;
+    uint32_t lo;
+    coef_image(c, q, lo);
     put_image(s_tab, sg, per, ci, q, lo);
   }
 }
@@ -916,7 +1019,8 @@ __device__ __forceinline__ void dec_wave_tile(const MacSeg& sg, const Unit& u, c
 template <int KC, int R, bool NT, int MODE, bool RAGGED = false>
 __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32_t* s_tab,
                                          const RaggedIdx* rg = nullptr) {
-  static_assert(!RAGGED || MODE == MAC_ENCODE || MODE == MAC_VERIFY, "ragged: encode and verify");
+  static_assert(!RAGGED || MODE == MAC_ENCODE || MODE == MAC_VERIFY || MODE == MAC_ROWS,
+                "ragged: encode, verify and the rows rebuild");
   constexpr bool VERIFY = MODE == MAC_VERIFY;  // the encode path, compare in place of stores
   constexpr bool COEF = MODE != MAC_ENCODE && !VERIFY;  // tables built in LDS from coefficients
   constexpr bool FUSED = MODE == MAC_FUSED;
@@ -930,7 +1034,9 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
   const uint32_t set_dw = R * kpad * 8;
 
   Unit u;
-  if constexpr (RAGGED) u = locate_ragged(sg, *rg, tile);
+  [[maybe_unused]] uint32_t ov = 0;  // ragged rows: the caller's block of set (lane % 64)
+  if constexpr (RAGGED && COEF) u = locate_ragged_rows(sg, *rg, tile, ov);
+  else if constexpr (RAGGED) u = locate_ragged(sg, *rg, tile);
   else u = locate(sg, tile);
   constexpr bool SOA = COEF;  // per-coefficient tables: split q / lo regions
   TabRef<SOA> tab;
@@ -1051,7 +1157,8 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
     // order, so the LDS copy then waits only for them), the KC shard loads
     // right behind; the barrier and table copy overlap the shard loads.
     uint32_t tv[COEF ? MAC_COEF_REGS : MAC_TAB_REGS];
-    if constexpr (COEF) load_coefs<R, KC>(sg, u, tv);
+    if constexpr (COEF && RAGGED) load_coefs_ragged<R, KC>(sg, u, ov, tv);
+    else if constexpr (COEF) load_coefs<R, KC>(sg, u, tv);
     else load_tables(sg, u, set_dw, tv);
     uint4 d[KC];
 #pragma unroll
@@ -1066,7 +1173,8 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
     __syncthreads();
     mac_chunk<KC, R>(acc, d, tab, kpad, 0);
   } else {
-    if constexpr (COEF) stage_images<R>(sg, u, s_tab);
+    if constexpr (COEF && RAGGED) stage_images_ragged<R>(sg, u, *rg, s_tab);
+    else if constexpr (COEF) stage_images<R>(sg, u, s_tab);
     else stage_tables(sg, u, set_dw, s_tab);
     __syncthreads();
     for (uint32_t j0 = 0; j0 < kin; j0 += KC) {
@@ -1319,6 +1427,17 @@ __global__ void __launch_bounds__(256) gf_verify_ragged_kernel(const RaggedLaunc
   uint64_t tile;
   if (!ragged_tile(L, tile)) return;
   mac_tile<KC, R, NT, MAC_VERIFY, true>(L.seg, tile, s_tab, &L.idx);
+}
+
+// The per-block-pattern ragged rebuild (memo_ec_rebuild_ragged): the rows
+// MAC over the capped ragged tiles, each non-empty block's tables built in
+// LDS from its decode rows.
+template <int KC, int R, bool NT>
+__global__ void __launch_bounds__(256) gf_mac_ragged_rows_kernel(const RaggedLaunch L) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];
+  uint64_t tile;
+  if (!ragged_tile(L, tile)) return;
+  mac_tile<KC, R, NT, MAC_ROWS, true>(L.seg, tile, s_tab, &L.idx);
 }
 
 #ifdef MEMO_EC_PERM_PROBE
@@ -2309,6 +2428,43 @@ hipError_t launch_mac_ragged(int KC, int R, bool verify, const RaggedLaunch& L, 
     case 12: return launch_ragged_r<12>(R, verify, L, grid, lds, st);
     case 14: return launch_ragged_r<14>(R, verify, L, grid, lds, st);
     case 16: return launch_ragged_r<16>(R, verify, L, grid, lds, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// gf_mac_ragged_rows_kernel, for the (KC, R) launch_mac serves.
+template <int KC>
+static hipError_t launch_rrows_r(int R, const RaggedLaunch& L, uint32_t grid, size_t lds,
+                                 hipStream_t st) {
+  switch (R) {
+#define MEMO_EC_R(x)                                                                           \
+  case x:                                                                                      \
+    hipLaunchKernelGGL((gf_mac_ragged_rows_kernel<KC, x, MAC_NT>), dim3(grid), dim3(256), lds, \
+                       st, L);                                                                 \
+    return hipGetLastError();
+    MEMO_EC_R(1) MEMO_EC_R(2) MEMO_EC_R(3) MEMO_EC_R(4)
+    default: break;
+  }
+  if constexpr (KC == 2 || KC == 3 || KC == 4 || KC == 10 || KC == 16) {
+    switch (R) {
+      MEMO_EC_R(6) MEMO_EC_R(8) MEMO_EC_R(12) MEMO_EC_R(16)
+      default: break;
+    }
+  }
+#undef MEMO_EC_R
+  return hipErrorInvalidValue;
+}
+hipError_t launch_mac_ragged_rows(int KC, int R, const RaggedLaunch& L, uint32_t grid, size_t lds,
+                                  hipStream_t st) {
+  switch (KC) {
+    case 2: return launch_rrows_r<2>(R, L, grid, lds, st);
+    case 3: return launch_rrows_r<3>(R, L, grid, lds, st);
+    case 4: return launch_rrows_r<4>(R, L, grid, lds, st);
+    case 6: return launch_rrows_r<6>(R, L, grid, lds, st);
+    case 10: return launch_rrows_r<10>(R, L, grid, lds, st);
+    case 12: return launch_rrows_r<12>(R, L, grid, lds, st);
+    case 14: return launch_rrows_r<14>(R, L, grid, lds, st);
+    case 16: return launch_rrows_r<16>(R, L, grid, lds, st);
     default: return hipErrorInvalidValue;
   }
 }

@@ -752,14 +752,15 @@ int idx_acquire(memo_ec_ctx* c, size_t bytes, memo_ec_ctx::IdxBuf** out) {
 // n + 1 entries and may start anywhere: a pipeline wave passes its part of
 // the call's arrays); data / parity / verdict: the first block's.  Builds
 // the index of every launch span, uploads it in one copy, then launches.
-int ragged_device(memo_ec_ctx* ctx, int k, int m, size_t n, const size_t* sizes, const uint64_t* off,
-                  const uint8_t* data, uint8_t* parity, uint32_t* verdict, hipStream_t st) {
+// The multiply is k -> m rows by the shared table image `tab` of bounds
+// (KC, R): the parity rows, or (memo_ec_rebuild_ragged with a shared
+// pattern, verdict null) that pattern's decode rows.
+int ragged_mac_device(memo_ec_ctx* ctx, int k, int m, int R, int KC, const uint32_t* tab, size_t n,
+                      const size_t* sizes, const uint64_t* off, const uint8_t* data, uint8_t* parity,
+                      uint32_t* verdict, hipStream_t st) {
   const bool verify = verdict != nullptr;
   if (verify) HIPCHK(hipMemsetAsync(verdict, 0, n * sizeof(uint32_t), st));
   if (off[n] == off[0]) return MEMO_EC_OK;
-  const int R = mac_rbound(m), KC = mac_kchunk(k, R);
-  const uint32_t* tab = nullptr;
-  if (int rc = encode_tables(ctx, k, m, R, KC, &tab)) return rc;
   uint64_t limit = 0x7fffffffull - MAC_TILE;
   if (ctx->opt.max_launch_tiles >= 1 && ctx->opt.max_launch_tiles < limit)
     limit = ctx->opt.max_launch_tiles;
@@ -828,6 +829,15 @@ int ragged_device(memo_ec_ctx* ctx, int k, int m, size_t n, const size_t* sizes,
   }
   const int rc2 = hip_rc(hipEventRecord(buf->ev, st));
   return rc ? rc : rc2;
+}
+
+int ragged_device(memo_ec_ctx* ctx, int k, int m, size_t n, const size_t* sizes, const uint64_t* off,
+                  const uint8_t* data, uint8_t* parity, uint32_t* verdict, hipStream_t st) {
+  const int R = mac_rbound(m), KC = mac_kchunk(k, R);
+  const uint32_t* tab = nullptr;
+  if (off[n] != off[0])
+    if (int rc = encode_tables(ctx, k, m, R, KC, &tab)) return rc;
+  return ragged_mac_device(ctx, k, m, R, KC, tab, n, sizes, off, data, parity, verdict, st);
 }
 
 DecodeArgs decode_args(const memo_ec_ctx* c, int k, int m, int e, size_t n, const uint8_t* surv_idx,
@@ -1727,6 +1737,230 @@ int rebuild_segments_impl(memo_ec_ctx* c, int nseg, const memo_ec_rebuild_segmen
   return deferred_rc(c, st);
 }
 
+// ---- Ragged rebuild (memo_ec_rebuild_ragged).
+
+// Table sets one tile of gf_mac_ragged_rows_kernel may build: what
+// plan_segment allows the flat uniform mapping (the staged coefficient
+// registers and the LDS budget).
+uint32_t ragged_rows_cap(int R, uint32_t kpad) {
+  return ragged::rows_cap((uint64_t)R * kpad, 256u * MAC_COEF_REGS, kLdsBudget);
+}
+
+// One ragged rebuild as the kernels see it: device (or zero-copy pinned)
+// survivors and outputs of n blocks, off[0..n] their byte offsets.
+struct RaggedRebuild {
+  int k = 0, m = 0, e = 0, R = 1, KC = 4;
+  const uint32_t* tab = nullptr;  // shared pattern: its table image; null: per-block patterns
+  // per-block patterns: n x k and n x e index bytes, device-readable, or
+  // (idx_host) in host memory: uploaded with the call's index
+  const uint8_t* sidx = nullptr;
+  const uint8_t* lidx = nullptr;
+  bool idx_host = false;
+  uint8_t* rows = nullptr;     // n x e x k bytes of decode-row scratch
+  uint32_t* status = nullptr;  // the decode's singular word
+};
+
+// Per-block patterns on stream st: the decode rows of all n blocks (the
+// decode zeroes a faulty block's rows, zero-size blocks are validated like
+// any other), then one gf_mac_ragged_rows_kernel launch per span.
+int ragged_rows_device(memo_ec_ctx* ctx, const RaggedRebuild& rb, size_t n, const size_t* sizes,
+                       const uint64_t* off, const uint8_t* surv, uint8_t* out, hipStream_t st) {
+  const int k = rb.k, e = rb.e, R = rb.R, KC = rb.KC;
+  const uint32_t kpad = kpad_of((uint32_t)k, KC);
+  const uint32_t cap = ragged_rows_cap(R, kpad);
+  uint64_t limit = 0x7fffffffull - MAC_TILE;
+  if (ctx->opt.max_launch_tiles >= 1 && ctx->opt.max_launch_tiles < limit)
+    limit = ctx->opt.max_launch_tiles;
+  const std::vector<ragged::Range> spans = ragged::cut_rows_spans(sizes, n, cap, limit);
+  // buffer layout: [surv_idx n x k | lost_idx n x e: idx_host] then per span
+  // [coff | desc | orig]
+  struct SpanAt {
+    ragged::Counts cnt;
+    size_t coff, desc, orig;
+  };
+  std::vector<SpanAt> at(spans.size());
+  const size_t sidx_b = n * (size_t)k, lidx_b = n * (size_t)e;
+  size_t bytes = rb.idx_host ? round16(sidx_b + lidx_b) : 0;
+  for (size_t i = 0; i < spans.size(); ++i) {
+    SpanAt& a = at[i];
+    a.cnt = ragged::rows_index_counts(sizes + spans[i].b0, spans[i].b1 - spans[i].b0, cap);
+    a.coff = bytes;
+    bytes += round16((a.cnt.nq + 1) * sizeof(uint64_t));
+    a.desc = bytes;
+    bytes += a.cnt.tiles * sizeof(ragged::RowsTileDesc);
+    a.orig = bytes;
+    bytes += round16(a.cnt.nq * sizeof(uint32_t));
+  }
+  const uint32_t* lw0 = nullptr;
+  if (int rc = lw0_table(ctx, k, rb.m, &lw0)) return rc;
+  memo_ec_ctx::IdxBuf* buf = nullptr;
+  if (int rc = idx_acquire(ctx, bytes, &buf)) return rc;
+  const uint8_t* sidx = rb.sidx;
+  const uint8_t* lidx = rb.lidx;
+  if (rb.idx_host) {
+    std::memcpy(buf->host, rb.sidx, sidx_b);
+    std::memcpy(buf->host + sidx_b, rb.lidx, lidx_b);
+    sidx = buf->dev;
+    lidx = buf->dev + sidx_b;
+  }
+  for (size_t i = 0; i < spans.size(); ++i)
+    ragged::build_rows_index(sizes + spans[i].b0, spans[i].b1 - spans[i].b0, cap,
+                             reinterpret_cast<uint64_t*>(buf->host + at[i].coff),
+                             reinterpret_cast<uint32_t*>(buf->host + at[i].orig),
+                             reinterpret_cast<ragged::RowsTileDesc*>(buf->host + at[i].desc));
+  buf->used = true;  // from here the buffer belongs to the enqueued work
+  int rc = bytes ? hip_rc(hipMemcpyAsync(buf->dev, buf->host, bytes, hipMemcpyHostToDevice, st))
+                 : MEMO_EC_OK;
+  if (!rc) {
+    const DecodeArgs a = decode_args(ctx, k, rb.m, e, n, sidx, lidx, rb.rows, rb.status, lw0);
+    rc = hip_rc(launch_decode_coef(a, st));
+  }
+  const size_t per = (size_t)R * kpad;
+  for (size_t i = 0; i < spans.size() && !rc; ++i) {
+    if (at[i].cnt.tiles == 0) continue;
+    const uint64_t o = off[spans[i].b0] - off[0];
+    RaggedLaunch L{};
+    MacSeg& s = L.seg;
+    s.in = surv + (uint64_t)k * o;
+    s.out = out + (uint64_t)e * o;
+    s.coef = rb.rows + spans[i].b0 * (size_t)e * k;
+    s.coef_bstride = (uint64_t)e * k;
+    s.coef_rows = (uint32_t)e;
+    s.coef_dense = 0;
+    s.lo_dw = (uint32_t)(cap * (per + 1) * 4);
+    s.n = at[i].cnt.nq;
+    s.tiles = at[i].cnt.tiles;
+    s.kin = (uint32_t)k;
+    s.r = (uint32_t)e;
+    s.kpad = kpad;
+    s.flat = 1;
+    L.idx.coff = reinterpret_cast<const uint64_t*>(buf->dev + at[i].coff);
+    L.idx.orig = reinterpret_cast<const uint32_t*>(buf->dev + at[i].orig);
+    L.idx.desc = reinterpret_cast<const uint4*>(buf->dev + at[i].desc);
+    L.xcd = s.tiles >= ctx->opt.xcd_min_tiles ? 1u : 0u;
+    rc = hip_rc(launch_mac_ragged_rows(KC, R, L, (uint32_t)s.tiles, cap * (per + 1) * 20, st));
+  }
+  const int rc2 = hip_rc(hipEventRecord(buf->ev, st));
+  return rc ? rc : rc2;
+}
+
+int ragged_rebuild_device(memo_ec_ctx* ctx, const RaggedRebuild& rb, size_t n, const size_t* sizes,
+                          const uint64_t* off, const uint8_t* surv, uint8_t* out, hipStream_t st) {
+  if (rb.tab)  // the ragged encode over the pattern's image, r = e
+    return ragged_mac_device(ctx, rb.k, rb.e, rb.R, rb.KC, rb.tab, n, sizes, off, surv, out, nullptr, st);
+  return ragged_rows_device(ctx, rb, n, sizes, off, surv, out, st);
+}
+
+size_t ragged_rows_bytes(const RaggedRebuild& rb, size_t n) {
+  return rb.tab ? 0 : round256(n * (size_t)rb.e * rb.k);
+}
+
+// Host-memory ragged rebuild: zero-copy on pinned memory for small calls,
+// else the copy pipeline with waves cut on block boundaries by the bytes a
+// block moves ((k + e) * S[b]); each wave's pattern bytes go up with its
+// index.  The singular word rides in the zero-copy slot, or comes back
+// behind the last wave's output (as rebuild_segments_impl's).
+int rebuild_ragged_host(memo_ec_ctx* c, RaggedRebuild rb, size_t n, const size_t* sizes,
+                        const uint64_t* off, const uint8_t* surv, uint8_t* out, bool pinned) {
+  const int k = rb.k, e = rb.e;
+  const bool per_block = rb.tab == nullptr;
+  const uint8_t* sidx = rb.sidx;
+  const uint8_t* lidx = rb.lidx;
+  rb.idx_host = true;
+  if (per_block) {
+    // device rebuilds still pending on the ctx stream use the same scratch
+    const hipError_t q = hipEventQuery(c->ev_order);
+    if (q == hipErrorNotReady) {
+      HIPCHK(hipStreamWaitEvent(c->sk, c->ev_order, 0));
+    } else if (q != hipSuccess) {
+      return hip_rc(q);
+    }
+  }
+  const uint64_t T = off[n];
+  const size_t in_b = (size_t)k * T, out_b = (size_t)e * T;
+  const size_t idx_b = per_block ? n * (size_t)(k + e) : 0;
+  if (in_b + out_b + idx_b + 64 <= zc_max_bytes(c)) {
+    const size_t payload = pinned ? 0 : in_b + out_b;
+    if (int rc = ensure_slots(c, 0, payload + 64)) return rc;
+    if (int rc = ensure_tabs(c, ragged_rows_bytes(rb, n))) return rc;
+    uint8_t* h = c->h_slot[0];
+    uint32_t* h_st = reinterpret_cast<uint32_t*>(h + ((payload + 3) & ~(size_t)3));
+    *h_st = 0;
+    const uint8_t* src = surv;
+    uint8_t* dst = out;
+    if (!pinned) {
+      par_memcpy(c, h, surv, in_b);
+      src = h;
+      dst = h + in_b;
+    }
+    rb.rows = reinterpret_cast<uint8_t*>(c->d_tabs);
+    rb.status = h_st;
+    if (int rc = ragged_rebuild_device(c, rb, n, sizes, off, src, dst, c->sk)) return rc;
+    HIPCHK(hipStreamSynchronize(c->sk));
+    if (!pinned) par_memcpy(c, out, dst, out_b);
+    return deferred_rc(c, __atomic_load_n(h_st, __ATOMIC_ACQUIRE));
+  }
+  const std::vector<ragged::Range> waves =
+      ragged::cut_waves(sizes, n, (uint64_t)(k + e), c->opt.pipe_bytes);
+  uint64_t tmax = 0;
+  size_t nmax = 0;
+  for (const auto& w : waves) {
+    tmax = std::max<uint64_t>(tmax, off[w.b1] - off[w.b0]);
+    nmax = std::max(nmax, w.b1 - w.b0);
+  }
+  const size_t slot = (size_t)(k + e) * tmax, o_off = (size_t)k * tmax;
+  const size_t rows_b = ragged_rows_bytes(rb, nmax);
+  if (int rc = ensure_slots(c, slot, pinned ? 0 : slot)) return rc;
+  if (int rc = ensure_tabs(c, kSlots * rows_b)) return rc;
+  auto wt = [&](size_t w) { return off[waves[w].b1] - off[waves[w].b0]; };
+  const int rc = run_waves(
+      c, waves.size(),
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const size_t nb = (size_t)k * wt(w);
+        if (!nb) return MEMO_EC_OK;
+        const uint8_t* src = surv + (size_t)k * off[waves[w].b0];
+        if (!pinned) {
+          par_memcpy(c, c->h_slot[s], src, nb);
+          src = c->h_slot[s];
+        }
+        return hip_rc(hipMemcpyAsync(c->d_slot[s], src, nb, hipMemcpyHostToDevice, st));
+      },
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const ragged::Range& r = waves[w];
+        RaggedRebuild wb = rb;
+        if (per_block) {
+          wb.sidx = sidx + r.b0 * (size_t)k;
+          wb.lidx = lidx + r.b0 * (size_t)e;
+          wb.rows = reinterpret_cast<uint8_t*>(c->d_tabs) + (size_t)s * rows_b;
+          wb.status = c->d_status + kStatusPipeline;
+        }
+        return ragged_rebuild_device(c, wb, r.b1 - r.b0, sizes + r.b0, off + r.b0, c->d_slot[s],
+                                     c->d_slot[s] + o_off, st);
+      },
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const size_t nb = (size_t)e * wt(w);
+        if (nb) {
+          uint8_t* dst = pinned ? out + (size_t)e * off[waves[w].b0] : c->h_slot[s] + o_off;
+          HIPCHK(hipMemcpyAsync(dst, c->d_slot[s] + o_off, nb, hipMemcpyDeviceToHost, st));
+        }
+        if (w + 1 == waves.size())
+          HIPCHK(hipMemcpyAsync(c->h_status, c->d_status + kStatusPipeline, sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, st));
+        return MEMO_EC_OK;
+      },
+      [&](int s, size_t w) {
+        if (!pinned)
+          par_memcpy(c, out + (size_t)e * off[waves[w].b0], c->h_slot[s] + o_off, (size_t)e * wt(w));
+      });
+  if (rc) return rc;
+  const uint32_t st = *c->h_status;
+  if (st) {
+    HIPCHK(hipMemsetAsync(c->d_status + kStatusPipeline, 0, sizeof(uint32_t), c->sd));
+    HIPCHK(hipStreamSynchronize(c->sd));
+  }
+  return deferred_rc(c, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1986,6 +2220,49 @@ int memo_ec_verify_ragged(memo_ec_ctx* c, int k, int m, size_t n, const size_t* 
                          c->stream);
   return verify_ragged_host(c, k, m, n, sizes, off.data(), data, parity, verdict,
                             where == MEMO_EC_HOST_PINNED);
+}
+
+int memo_ec_rebuild_ragged(memo_ec_ctx* c, int k, int m, size_t n, const size_t* sizes,
+                           const uint8_t* surv_idx, const uint8_t* surv, const uint8_t* lost_idx,
+                           int e, int uniform, uint8_t* out, int where) {
+  if (int rc = check_km(k, m)) return rc;
+  std::vector<uint64_t> off;
+  if (int rc = ragged_check(k, m, n, sizes, off)) return rc;
+  if (!c || e < 0 || e > m) return MEMO_EC_EINVAL;
+  if (where != MEMO_EC_DEVICE && where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED)
+    return MEMO_EC_EINVAL;
+  if (e == 0 || n == 0) return MEMO_EC_OK;
+  if (!surv_idx || !lost_idx) return MEMO_EC_EINVAL;
+  const uint64_t T = off[n];
+  if (T && (!surv || !out)) return MEMO_EC_EINVAL;
+  if (shard_misaligned(where, surv) || shard_misaligned(where, out)) return MEMO_EC_EINVAL;
+  if (!uniform && too_big(n, (size_t)e * k + k + e)) return MEMO_EC_ERANGE;
+  DeviceGuard g(c->device);
+  RaggedRebuild rb;
+  rb.k = k;
+  rb.m = m;
+  rb.e = e;
+  rb.R = mac_rbound(e);
+  rb.KC = mac_kchunk(k, rb.R);
+  if (uniform) {
+    // the pattern is decoded (and its image cached) before anything is enqueued
+    ++c->call_seq;
+    if (int rc = pattern_tables(c, k, m, surv_idx, lost_idx, e, rb.R, rb.KC, &rb.tab)) return rc;
+    if (T == 0) return MEMO_EC_OK;
+  } else {
+    rb.sidx = surv_idx;
+    rb.lidx = lost_idx;
+  }
+  if (where != MEMO_EC_DEVICE)
+    return rebuild_ragged_host(c, rb, n, sizes, off.data(), surv, out, where == MEMO_EC_HOST_PINNED);
+  if (!uniform) {
+    if (int rc = ensure_tabs(c, ragged_rows_bytes(rb, n))) return rc;
+    rb.rows = reinterpret_cast<uint8_t*>(c->d_tabs);
+    rb.status = c->d_status + kStatusDevice;
+  }
+  if (int rc = ragged_rebuild_device(c, rb, n, sizes, off.data(), surv, out, c->stream)) return rc;
+  // marks the scratch busy until this rebuild is done (host calls check it)
+  return uniform ? MEMO_EC_OK : hip_rc(hipEventRecord(c->ev_order, c->stream));
 }
 
 int memo_ec_stream_probe(memo_ec_ctx* c, int kin, int r, size_t S, size_t n, const uint8_t* in,

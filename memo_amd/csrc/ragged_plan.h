@@ -1,8 +1,9 @@
 // ragged_plan.h -- GPU-free planning of ragged batches (memo_ec_encode_ragged /
-// memo_ec_verify_ragged): size validation, prefix sums, launch spans, pipeline
-// waves and the per-tile descriptors the ragged kernels read.  Plain C++17,
-// no HIP include: tests/test_ragged_plan.py builds it into a stand-alone
-// program with the host sanitizers.
+// memo_ec_verify_ragged / memo_ec_rebuild_ragged): size validation, prefix
+// sums, launch spans, pipeline waves and the per-tile descriptors the ragged
+// kernels read.  Plain C++17, no HIP include: tests/test_ragged_plan.py and
+// tests/test_ragged_rebuild_plan.py build it into stand-alone programs with
+// the host sanitizers.
 //
 // A ragged batch of n blocks has shard sizes S[b] (multiples of 64, < 2^32,
 // 0 allowed), packed back to back: off[b] = S[0] + ... + S[b-1], T = off[n].
@@ -164,6 +165,150 @@ inline Index build_index(const size_t* sizes, size_t n) {
   ix.orig.resize(c.nq);
   ix.desc.resize(c.tiles);
   build_index(sizes, n, ix.coff.data(), ix.orig.data(), ix.desc.data());
+  return ix;
+}
+
+// ---- Ragged rebuild with per-block patterns (memo_ec_rebuild_ragged).
+// Every non-empty block of a tile has a table set of its own, so a tile
+// touches at most `cap` blocks (rows_cap): a tile starts where the previous
+// one ended and covers 256 columns, or ends at the start of non-empty block
+// q_first + cap if that comes first.  A tile cut by the cap ends on a block
+// boundary and its trailing lanes are idle; tiles are no longer at 256 * t,
+// so the descriptor carries the tile's first column.
+
+// Table sets one tile may build: `per` = R * kpad coefficient slots per set,
+// `stage_slots` the coefficients a tile stages through registers, LDS of
+// (per + 1) * 20 bytes per set within `lds_bytes`; never above the 64 blocks
+// 256 columns can touch.
+inline uint32_t rows_cap(uint64_t per, uint64_t stage_slots, uint64_t lds_bytes) {
+  uint64_t cap = 64;
+  if (stage_slots / per < cap) cap = stage_slots / per;
+  if (lds_bytes / ((per + 1) * 20) < cap) cap = lds_bytes / ((per + 1) * 20);
+  return cap < 1 ? 1u : (uint32_t)cap;
+}
+
+struct RowsTileDesc {
+  uint32_t q_first;  // non-empty block holding the tile's first column
+  uint32_t nblk;     // non-empty blocks the tile's columns touch (1..cap)
+  uint32_t c0;       // the tile's first column, inside block q_first
+  uint32_t cols;     // columns of block q_first (S / 16)
+  uint64_t col;      // the tile's first column in the span's column space
+  uint32_t ncols;    // the tile's columns (1..256)
+  uint32_t pad;
+};
+static_assert(sizeof(RowsTileDesc) == 32, "read as two 16-byte loads");
+
+// Tiles of a column space fed one non-empty block at a time.
+struct RowsCounter {
+  uint32_t cap = 1;
+  uint64_t nq = 0, cols = 0, tiles = 0;
+  uint32_t tcols = 0, tblk = 0;  // the open tile's columns and blocks
+  explicit RowsCounter(uint32_t cap_) : cap(cap_ ? cap_ : 1) {}
+  void add(uint64_t c) {  // a block of c > 0 columns
+    ++nq;
+    cols += c;
+    bool fresh = true;  // the block's first piece: counts against the cap
+    while (c) {
+      if (tiles == 0 || tcols == kTileCols || (fresh && tblk == cap)) {
+        ++tiles;
+        tcols = 0;
+        tblk = 0;
+      }
+      fresh = false;
+      if (tcols == 0 && c >= kTileCols) {  // whole tiles inside the block
+        const uint64_t w = c / kTileCols;
+        tiles += w - 1;
+        tcols = kTileCols;
+        tblk = 1;
+        c -= w * kTileCols;
+        continue;
+      }
+      const uint64_t take = c < kTileCols - tcols ? c : kTileCols - tcols;
+      tcols += (uint32_t)take;
+      ++tblk;
+      c -= take;
+    }
+  }
+};
+
+inline Counts rows_index_counts(const size_t* sizes, size_t n, uint32_t cap) {
+  RowsCounter rc(cap);
+  for (size_t b = 0; b < n; ++b)
+    if (sizes[b]) rc.add((uint64_t)sizes[b] / 16);
+  Counts c;
+  c.nq = rc.nq;
+  c.cols = rc.cols;
+  c.tiles = rc.tiles;
+  return c;
+}
+
+// cut_spans for the capped tiles: each span of at most tile_limit tiles as
+// rows_index_counts counts them (tiles restart at a span's first column).
+inline std::vector<Range> cut_rows_spans(const size_t* sizes, size_t n, uint32_t cap,
+                                         uint64_t tile_limit,
+                                         uint64_t block_limit = kMaxSpanBlocks) {
+  std::vector<Range> out;
+  size_t b0 = 0;
+  RowsCounter cur(cap);
+  for (size_t b = 0; b < n; ++b) {
+    RowsCounter nxt = cur;
+    if (sizes[b]) nxt.add((uint64_t)sizes[b] / 16);
+    if (b > b0 && (nxt.tiles > tile_limit || b - b0 >= block_limit)) {
+      out.push_back({b0, b});
+      b0 = b;
+      nxt = RowsCounter(cap);
+      if (sizes[b]) nxt.add((uint64_t)sizes[b] / 16);
+    }
+    cur = nxt;
+  }
+  if (n > b0) out.push_back({b0, n});
+  return out;
+}
+
+// Fills coff[nq + 1], orig[nq] and desc[tiles] (rows_index_counts' figures)
+// of the span `sizes[0..n)`.
+inline void build_rows_index(const size_t* sizes, size_t n, uint32_t cap, uint64_t* coff,
+                             uint32_t* orig, RowsTileDesc* desc) {
+  if (cap < 1) cap = 1;
+  uint64_t nq = 0, cols = 0;
+  for (size_t b = 0; b < n; ++b)
+    if (sizes[b]) {
+      orig[nq] = (uint32_t)b;
+      coff[nq++] = cols;
+      cols += (uint64_t)sizes[b] / 16;
+    }
+  coff[nq] = cols;
+  uint64_t q = 0, t = 0;
+  for (uint64_t c = 0; c < cols; ++t) {
+    while (coff[q + 1] <= c) ++q;
+    uint64_t end = c + kTileCols < cols ? c + kTileCols : cols;
+    if (q + cap <= nq && coff[q + cap] < end) end = coff[q + cap];
+    uint64_t qe = q;
+    while (coff[qe + 1] < end) ++qe;
+    RowsTileDesc& d = desc[t];
+    d.q_first = (uint32_t)q;
+    d.nblk = (uint32_t)(qe - q + 1);
+    d.c0 = (uint32_t)(c - coff[q]);
+    d.cols = (uint32_t)(coff[q + 1] - coff[q]);
+    d.col = c;
+    d.ncols = (uint32_t)(end - c);
+    d.pad = 0;
+    c = end;
+  }
+}
+
+struct RowsIndex {
+  std::vector<uint64_t> coff;
+  std::vector<uint32_t> orig;
+  std::vector<RowsTileDesc> desc;
+};
+inline RowsIndex build_rows_index(const size_t* sizes, size_t n, uint32_t cap) {
+  const Counts c = rows_index_counts(sizes, n, cap);
+  RowsIndex ix;
+  ix.coff.resize(c.nq + 1);
+  ix.orig.resize(c.nq);
+  ix.desc.resize(c.tiles);
+  build_rows_index(sizes, n, cap, ix.coff.data(), ix.orig.data(), ix.desc.data());
   return ix;
 }
 

@@ -80,7 +80,7 @@ EXPORTS = [
     "memo_ec_version", "memo_ec_device_count", "memo_ec_rebuild_segments",
     "memo_ec_ctx_set_option", "memo_ec_ctx_get_option", "memo_ec_build_id",
     "memo_ec_device_identity", "memo_ec_stream_probe", "memo_ec_verify_batch",
-    "memo_ec_encode_ragged", "memo_ec_verify_ragged",
+    "memo_ec_encode_ragged", "memo_ec_verify_ragged", "memo_ec_rebuild_ragged",
 ]
 
 # memo_ec_verify_batch verdict words: MEMO_EC_VERDICT_UNLOCATED of the header.
@@ -152,6 +152,9 @@ def _lib():
                                                 _u8p, _u8p, c_int]
             L.memo_ec_verify_ragged.argtypes = [ctypes.c_void_p, c_int, c_int, _sz, ctypes.c_void_p,
                                                 _u8p, _u8p, ctypes.c_void_p, c_int]
+        if hasattr(L, "memo_ec_rebuild_ragged"):
+            L.memo_ec_rebuild_ragged.argtypes = [ctypes.c_void_p, c_int, c_int, _sz, ctypes.c_void_p,
+                                                 _u8p, _u8p, _u8p, c_int, c_int, _u8p, c_int]
         _LIB = L
     return _LIB
 
@@ -498,6 +501,53 @@ class Codec:
         where = DEVICE if sw == DEVICE else (HOST_PINNED if sw == ow == HOST_PINNED else HOST)
         _check(_lib().memo_ec_rebuild_uniform(self._ctx, k, m, S, n, si.ctypes.data, sp,
                                               li.ctypes.data, len(li), op, where), "rebuild_uniform")
+        return out
+
+    def rebuild_ragged(self, k, m, sizes, surv_idx, surv, lost_idx, out, uniform=False):
+        """memo_ec_rebuild_ragged: Codec.rebuild over blocks of their own shard
+        sizes packed back to back (the layout of encode_ragged): surv holds
+        k * T and out e * T bytes, survivor t of block b at k * off[b] +
+        t * sizes[b], rebuilt shard r at e * off[b] + r * sizes[b].
+        surv_idx (n x k) and lost_idx (n x e) live where the shards do; with
+        uniform=True they are host sequences of k and e indices, one pattern
+        for every block.  Flat uint8 buffers; device (async) or host (sync)."""
+        sz = _sizes(sizes)
+        n = len(sz)
+        if n and (sz % 64).any():
+            raise ValueError("sizes must be multiples of 64")
+        if n and int(sz.max()) >= 1 << 32:
+            raise ValueError("sizes must be below 2^32")
+        sp, sw = _ptr(surv)
+        op, ow = _ptr(out)
+        if (sw == DEVICE) != (ow == DEVICE):
+            raise ValueError("surv and out must both be device or both host buffers")
+        keep = []
+        if uniform:
+            si = np.ascontiguousarray(np.asarray(surv_idx, dtype=np.uint8).reshape(-1))
+            li = np.ascontiguousarray(np.asarray(lost_idx, dtype=np.uint8).reshape(-1))
+            if len(si) != k:
+                raise ValueError("surv_idx has %d entries, k = %d" % (len(si), k))
+            e = len(li)
+            keep = [si, li]
+            ip, lp = si.ctypes.data, li.ctypes.data
+        else:
+            if len(surv_idx.shape) != 2 or tuple(surv_idx.shape) != (n, k):
+                raise ValueError("surv_idx must be n x k = %d x %d" % (n, k))
+            if len(lost_idx.shape) != 2 or lost_idx.shape[0] != n:
+                raise ValueError("lost_idx must be n x e with n = %d" % n)
+            e = int(lost_idx.shape[1])
+            ip, iw = _ptr(surv_idx)
+            lp, lw = _ptr(lost_idx)
+            if (iw == DEVICE) != (sw == DEVICE) or (lw == DEVICE) != (sw == DEVICE):
+                raise ValueError("surv_idx and lost_idx must live where the shards do")
+        if e > m:
+            raise ValueError("lost_idx names %d shards, m = %d" % (e, m))
+        _check_ragged_len(sz, ((surv, k, "surv"), (out, e, "out")))
+        where = DEVICE if sw == DEVICE else (HOST_PINNED if sw == ow == HOST_PINNED else HOST)
+        _check(_lib().memo_ec_rebuild_ragged(self._ctx, k, m, n, sz.ctypes.data, ip or None, sp or None,
+                                             lp or None, e, int(bool(uniform)), op or None, where),
+               "rebuild_ragged")
+        del keep
         return out
 
     def decode_rows(self, k, m, surv_idx, lost_idx, rows):
