@@ -620,22 +620,18 @@ int ensure_slots(memo_ec_ctx* ctx, size_t dev_bytes, size_t host_bytes) {
   return MEMO_EC_OK;
 }
 
-// Host-memory calls moving at most this many bytes (in + out) run their
-// kernels on pinned host memory directly, with no DMA copies: 5-40% less
-// time than the copy pipeline up to ~8 MiB of input, more beyond, where the
-// pipeline's copy overlap and threaded bounce copies win
-// (profiles/r01_zero_copy_probe.jsonl).  The ctx's MEMO_EC_OPT_ZERO_COPY_BYTES
-// (0 disables).
-size_t zc_max_bytes(const memo_ec_ctx* c) { return c->opt.zc_max_bytes; }
-
-// Largest batch (blocks) one MAC launch takes: tiles must fit a 31-bit grid.
+// Tiles one MAC launch takes: they must fit a 31-bit grid.
 // MEMO_EC_OPT_MAX_LAUNCH_TILES lowers the bound so tests can reach the split
 // path without a 2^31-tile batch.
+uint64_t launch_tile_limit(const memo_ec_ctx* c) {
+  const uint64_t limit = 0x7fffffffull - MAC_TILE;
+  return c->opt.max_launch_tiles >= 1 && c->opt.max_launch_tiles < limit ? c->opt.max_launch_tiles : limit;
+}
+
+// Largest batch (blocks of S-byte shards) one MAC launch takes.
 size_t max_blocks_per_launch(const memo_ec_ctx* c, size_t S) {
-  uint64_t limit = 0x7fffffffull - MAC_TILE;
-  if (c->opt.max_launch_tiles >= 1 && c->opt.max_launch_tiles < limit) limit = c->opt.max_launch_tiles;
   const uint64_t per = (S / 16 + MAC_TILE - 1) / MAC_TILE + 1;
-  return (size_t)std::max<uint64_t>(1, limit / per);
+  return (size_t)std::max<uint64_t>(1, launch_tile_limit(c) / per);
 }
 
 // fn(b0, cnt) over n blocks of S-byte shards, in spans one MAC launch takes.
@@ -747,6 +743,76 @@ int idx_acquire(memo_ec_ctx* c, size_t bytes, memo_ec_ctx::IdxBuf** out) {
   return MEMO_EC_OK;
 }
 
+// The two descriptor kinds of a ragged launch: how its spans are cut and
+// counted and its index built (ragged_plan.h).
+struct TileKind {  // 256-column tiles: encode, verify, shared-pattern rebuild
+  static constexpr size_t kDesc = sizeof(ragged::TileDesc);
+  std::vector<ragged::Range> spans(const size_t* sz, size_t n, uint64_t limit) const {
+    return ragged::cut_spans(sz, n, limit);
+  }
+  ragged::Counts counts(const size_t* sz, size_t n) const { return ragged::index_counts(sz, n); }
+  void build(const size_t* sz, size_t n, uint64_t* coff, uint32_t* orig, void* desc) const {
+    ragged::build_index(sz, n, coff, orig, static_cast<ragged::TileDesc*>(desc));
+  }
+};
+struct RowsKind {  // tiles of at most `cap` blocks: per-block patterns
+  static constexpr size_t kDesc = sizeof(ragged::RowsTileDesc);
+  uint32_t cap;
+  std::vector<ragged::Range> spans(const size_t* sz, size_t n, uint64_t limit) const {
+    return ragged::cut_rows_spans(sz, n, cap, limit);
+  }
+  ragged::Counts counts(const size_t* sz, size_t n) const { return ragged::rows_index_counts(sz, n, cap); }
+  void build(const size_t* sz, size_t n, uint64_t* coff, uint32_t* orig, void* desc) const {
+    ragged::build_rows_index(sz, n, cap, coff, orig, static_cast<ragged::RowsTileDesc*>(desc));
+  }
+};
+
+// One launch span of a ragged call and its index in device memory.
+struct SpanIdx {
+  size_t b0 = 0;  // the span's first block
+  ragged::Counts cnt;
+  RaggedIdx idx{};
+};
+
+// The index of a ragged call over n blocks on stream st: cuts the launch
+// spans, lays out [head | per span: coff | desc | orig] in an index buffer
+// (`head(host)` fills head_b bytes of the call's own), builds it, uploads it
+// in one copy, runs `launch(head in device memory, spans)` and records the
+// buffer's event behind what that enqueued.
+template <class Kind, class Head, class Launch>
+int with_ragged_index(memo_ec_ctx* ctx, const Kind& kind, const size_t* sizes, size_t n, size_t head_b,
+                      Head head, hipStream_t st, Launch launch) {
+  const std::vector<ragged::Range> spans = kind.spans(sizes, n, launch_tile_limit(ctx));
+  std::vector<SpanIdx> at(spans.size());
+  std::vector<size_t> coff(spans.size());  // byte offsets; desc and orig follow
+  size_t bytes = round16(head_b);
+  for (size_t i = 0; i < spans.size(); ++i) {
+    at[i].b0 = spans[i].b0;
+    at[i].cnt = kind.counts(sizes + spans[i].b0, spans[i].b1 - spans[i].b0);
+    coff[i] = bytes;
+    bytes += round16((at[i].cnt.nq + 1) * sizeof(uint64_t)) + at[i].cnt.tiles * Kind::kDesc +
+             round16(at[i].cnt.nq * sizeof(uint32_t));
+  }
+  memo_ec_ctx::IdxBuf* buf = nullptr;
+  if (int rc = idx_acquire(ctx, bytes, &buf)) return rc;
+  head(buf->host);
+  for (size_t i = 0; i < spans.size(); ++i) {
+    const size_t desc = coff[i] + round16((at[i].cnt.nq + 1) * sizeof(uint64_t));
+    const size_t orig = desc + at[i].cnt.tiles * Kind::kDesc;
+    kind.build(sizes + spans[i].b0, spans[i].b1 - spans[i].b0,
+               reinterpret_cast<uint64_t*>(buf->host + coff[i]),
+               reinterpret_cast<uint32_t*>(buf->host + orig), buf->host + desc);
+    at[i].idx.coff = reinterpret_cast<const uint64_t*>(buf->dev + coff[i]);
+    at[i].idx.orig = reinterpret_cast<const uint32_t*>(buf->dev + orig);
+    at[i].idx.desc = reinterpret_cast<const uint4*>(buf->dev + desc);
+  }
+  buf->used = true;  // from here the buffer belongs to the enqueued work
+  int rc = bytes ? hip_rc(hipMemcpyAsync(buf->dev, buf->host, bytes, hipMemcpyHostToDevice, st)) : MEMO_EC_OK;
+  if (!rc) rc = launch(buf->dev, at);
+  const int rc2 = hip_rc(hipEventRecord(buf->ev, st));
+  return rc ? rc : rc2;
+}
+
 // Device-resident ragged encode (verdict null) or verify of n blocks on
 // stream st.  sizes / off: the blocks' shard sizes and byte offsets (off has
 // n + 1 entries and may start anywhere: a pipeline wave passes its part of
@@ -761,74 +827,47 @@ int ragged_mac_device(memo_ec_ctx* ctx, int k, int m, int R, int KC, const uint3
   const bool verify = verdict != nullptr;
   if (verify) HIPCHK(hipMemsetAsync(verdict, 0, n * sizeof(uint32_t), st));
   if (off[n] == off[0]) return MEMO_EC_OK;
-  uint64_t limit = 0x7fffffffull - MAC_TILE;
-  if (ctx->opt.max_launch_tiles >= 1 && ctx->opt.max_launch_tiles < limit)
-    limit = ctx->opt.max_launch_tiles;
-  const std::vector<ragged::Range> spans = ragged::cut_spans(sizes, n, limit);
-  // buffer layout: [boff (n + 1) x 8: verify] then per span [coff | desc | orig]
-  struct SpanAt {
-    ragged::Counts cnt;
-    size_t coff, desc, orig;
-  };
-  std::vector<SpanAt> at(spans.size());
-  size_t bytes = verify ? round16((n + 1) * sizeof(uint64_t)) : 0;
-  for (size_t i = 0; i < spans.size(); ++i) {
-    SpanAt& a = at[i];
-    a.cnt = ragged::index_counts(sizes + spans[i].b0, spans[i].b1 - spans[i].b0);
-    a.coff = bytes;
-    bytes += round16((a.cnt.nq + 1) * sizeof(uint64_t));
-    a.desc = bytes;
-    bytes += a.cnt.tiles * sizeof(ragged::TileDesc);
-    a.orig = bytes;
-    bytes += round16(a.cnt.nq * sizeof(uint32_t));
-  }
-  memo_ec_ctx::IdxBuf* buf = nullptr;
-  if (int rc = idx_acquire(ctx, bytes, &buf)) return rc;
-  if (verify) {
-    uint64_t* boff = reinterpret_cast<uint64_t*>(buf->host);
-    for (size_t b = 0; b <= n; ++b) boff[b] = (off[b] - off[0]) / 16;
-  }
-  for (size_t i = 0; i < spans.size(); ++i)
-    ragged::build_index(sizes + spans[i].b0, spans[i].b1 - spans[i].b0,
-                        reinterpret_cast<uint64_t*>(buf->host + at[i].coff),
-                        reinterpret_cast<uint32_t*>(buf->host + at[i].orig),
-                        reinterpret_cast<ragged::TileDesc*>(buf->host + at[i].desc));
-  buf->used = true;  // from here the buffer belongs to the enqueued work
-  int rc = hip_rc(hipMemcpyAsync(buf->dev, buf->host, bytes, hipMemcpyHostToDevice, st));
-  for (size_t i = 0; i < spans.size() && !rc; ++i) {
-    if (at[i].cnt.tiles == 0) continue;
-    const uint64_t o = off[spans[i].b0] - off[0];
-    RaggedLaunch L{};
-    MacSeg& s = L.seg;
-    s.in = data + (uint64_t)k * o;
-    s.out = parity + (uint64_t)m * o;
-    s.tab = tab;
-    s.n = at[i].cnt.nq;
-    s.tiles = at[i].cnt.tiles;
-    s.kin = (uint32_t)k;
-    s.r = (uint32_t)m;
-    s.kpad = kpad_of((uint32_t)k, KC);
-    s.flat = 1;
-    s.verdict = verify ? verdict + spans[i].b0 : nullptr;
-    L.idx.coff = reinterpret_cast<const uint64_t*>(buf->dev + at[i].coff);
-    L.idx.orig = reinterpret_cast<const uint32_t*>(buf->dev + at[i].orig);
-    L.idx.desc = reinterpret_cast<const uint4*>(buf->dev + at[i].desc);
-    L.xcd = s.tiles >= ctx->opt.xcd_min_tiles ? 1u : 0u;
-    rc = hip_rc(launch_mac_ragged(KC, R, verify, L, (uint32_t)s.tiles, (size_t)R * s.kpad * 32, st));
-  }
-  if (!rc && verify) {
-    RaggedLocateArgs ra{};
-    ra.a.data = data;
-    ra.a.parity = parity;
-    ra.a.verdict = verdict;
-    ra.a.n = n;
-    ra.a.k = (uint32_t)k;
-    ra.a.m = (uint32_t)m;
-    ra.boff = reinterpret_cast<const uint64_t*>(buf->dev);
-    rc = hip_rc(launch_verify_locate_ragged(ra, st));
-  }
-  const int rc2 = hip_rc(hipEventRecord(buf->ev, st));
-  return rc ? rc : rc2;
+  const size_t head_b = verify ? (n + 1) * sizeof(uint64_t) : 0;  // verify: boff
+  return with_ragged_index(
+      ctx, TileKind{}, sizes, n, head_b,
+      [&](uint8_t* host) {
+        if (!verify) return;
+        uint64_t* boff = reinterpret_cast<uint64_t*>(host);
+        for (size_t b = 0; b <= n; ++b) boff[b] = (off[b] - off[0]) / 16;
+      },
+      st, [&](const uint8_t* head, const std::vector<SpanIdx>& spans) -> int {
+        for (const SpanIdx& sp : spans) {
+          if (sp.cnt.tiles == 0) continue;
+          const uint64_t o = off[sp.b0] - off[0];
+          RaggedLaunch L{};
+          MacSeg& s = L.seg;
+          s.in = data + (uint64_t)k * o;
+          s.out = parity + (uint64_t)m * o;
+          s.tab = tab;
+          s.n = sp.cnt.nq;
+          s.tiles = sp.cnt.tiles;
+          s.kin = (uint32_t)k;
+          s.r = (uint32_t)m;
+          s.kpad = kpad_of((uint32_t)k, KC);
+          s.flat = 1;
+          s.verdict = verify ? verdict + sp.b0 : nullptr;
+          L.idx = sp.idx;
+          L.xcd = s.tiles >= ctx->opt.xcd_min_tiles ? 1u : 0u;
+          if (int rc = hip_rc(launch_mac_ragged(KC, R, verify, L, (uint32_t)s.tiles,
+                                                (size_t)R * s.kpad * 32, st)))
+            return rc;
+        }
+        if (!verify) return MEMO_EC_OK;
+        RaggedLocateArgs ra{};
+        ra.a.data = data;
+        ra.a.parity = parity;
+        ra.a.verdict = verdict;
+        ra.a.n = n;
+        ra.a.k = (uint32_t)k;
+        ra.a.m = (uint32_t)m;
+        ra.boff = reinterpret_cast<const uint64_t*>(head);
+        return hip_rc(launch_verify_locate_ragged(ra, st));
+      });
 }
 
 int ragged_device(memo_ec_ctx* ctx, int k, int m, size_t n, const size_t* sizes, const uint64_t* off,
@@ -940,222 +979,204 @@ int run_waves(memo_ec_ctx* c, size_t nw, In in, Run run, Out out, Done done) {
   return MEMO_EC_OK;
 }
 
-// run_waves over batches of nb of n blocks: the callbacks get (slot, first
-// block, blocks[, stream]).
-template <class In, class Run, class Out, class Done>
-int run_pipeline(memo_ec_ctx* c, size_t n, size_t nb, In in, Run run, Out out, Done done) {
-  auto span = [&](size_t w, size_t& b0, size_t& cn) {
-    b0 = w * nb;
-    cn = std::min(nb, n - b0);
-  };
-  size_t b0, cn;
-  return run_waves(
-      c, (n + nb - 1) / nb,
-      [&](int s, size_t w, hipStream_t st) { span(w, b0, cn); return in(s, b0, cn, st); },
-      [&](int s, size_t w, hipStream_t st) { span(w, b0, cn); return run(s, b0, cn, st); },
-      [&](int s, size_t w, hipStream_t st) { span(w, b0, cn); return out(s, b0, cn, st); },
-      [&](int s, size_t w) {
-        size_t x0, xn;
-        span(w, x0, xn);
-        done(s, x0, xn);
-      });
+// What a call reports once its work is done: the ctx's deferred error, else
+// ESINGULAR when its status word `st` has the singular bit.
+int deferred_rc(memo_ec_ctx* ctx, uint32_t st) {
+  int rc = ctx->deferred;
+  ctx->deferred = 0;
+  if (rc == MEMO_EC_OK && (st & 1u)) rc = MEMO_EC_ESINGULAR;
+  return rc;
 }
 
-// A host-memory call of one multiply-accumulate over n blocks of in_b bytes
-// in and out_b bytes out (the encode): `run(src, dst, cnt, st)`
-// enqueues the kernels for cnt blocks of device- or pinned-memory src/dst.
-// Small calls run zero-copy on pinned memory; larger ones through the
-// 3-stage copy pipeline.
+// ---- Host-memory calls (MEMO_EC_HOST, MEMO_EC_HOST_PINNED): every entry
+// point describes its data movement as waves of extents (ragged_plan.h:
+// stage::Plan) and hands run_staged a callback that launches a wave's kernels.
+
+// Host-memory calls moving at most the ctx's MEMO_EC_OPT_ZERO_COPY_BYTES (0
+// disables) run their kernels on pinned host memory directly, with no DMA
+// copies: 5-40% less time than the copy pipeline up to ~8 MiB of input, more
+// beyond, where the pipeline's copy overlap and threaded bounce copies win
+// (profiles/r01_zero_copy_probe.jsonl).  `bytes`: everything the call moves,
+// plus 64 for a status word.
+bool zero_copy(const memo_ec_ctx* c, size_t bytes) { return bytes <= c->opt.zc_max_bytes; }
+
+// The waves of a host-memory call over n items (blocks; a segment rebuild's
+// chunks), item b weighing per * size(b): a zero-copy call is one wave,
+// whatever its size, a pipelined one is cut by the ctx's pipeline batch.
+template <class Size>
+std::vector<ragged::Range> call_waves(const memo_ec_ctx* c, bool zc, size_t n, uint64_t per, Size size) {
+  if (zc) return {ragged::Range{0, n}};
+  return ragged::cut_waves_by(size, n, per, c->opt.pipe_bytes);
+}
+
+// Device rebuilds still pending on the ctx stream use the same scratch
+// (d_tabs: per-block decode rows) as a host-memory rebuild's kernels: the
+// compute stream waits for them.
+int wait_device_rebuilds(memo_ec_ctx* c) {
+  const hipError_t q = hipEventQuery(c->ev_order);
+  if (q == hipErrorNotReady) HIPCHK(hipStreamWaitEvent(c->sk, c->ev_order, 0));
+  return q == hipErrorNotReady ? MEMO_EC_OK : hip_rc(q);
+}
+
+// What one wave's kernels get: v(i), extent i of the wave where they reach it
+// (its place in the device slot; zero-copy: the caller's pinned buffer or its
+// place in the host slot), the wave's part of the rebuild scratch and the
+// word its decodes flag a singular block in.
+struct StageView {
+  const stage::Extent* ext;
+  bool zc;
+  uint8_t* base;  // the device slot; zero-copy: the host slot
+  uint8_t* scratch;
+  uint32_t* status;
+  uint8_t* operator()(size_t i) const {
+    const stage::Extent& e = ext[i];
+    if (!zc) return base + e.at;
+    return e.hat == stage::kNone ? static_cast<uint8_t*>(e.host) : base + e.hat;
+  }
+};
+
+// Runs a host-memory call.  `pl`: its waves (zc: one); `scratch`: bytes of
+// d_tabs a wave's kernels use; `status`: the call reports what its kernels
+// flag in StageView::status (a rebuild's singular blocks); run(w, view, st)
+// enqueues wave w's kernels on st.
+//  - zc: the kernels read the wave from, and write their output to, pinned
+//    host memory over PCIe -- no DMA copies to wait for.  A pinned caller's
+//    buffers are used where they lie, a pageable caller's are copied through
+//    the host slot; the status word rides behind the slot.
+//  - else the 3-stage pipeline of run_waves: bounce copies of pageable
+//    memory and kSlot bytes, HtoD, kernels, DtoH, bounce copies back.  A
+//    pinned caller's buffers are the DMA's source and target.
 template <class Run>
-int host_mac(memo_ec_ctx* c, size_t n, size_t in_b, size_t out_b, const uint8_t* data,
-             uint8_t* out, bool pinned, Run run) {
-  if (n * (in_b + out_b) <= zc_max_bytes(c)) {
-    // Small call: the kernel reads the blocks from, and writes its output
-    // to, pinned host memory over PCIe -- no DMA copies to wait for.
-    if (int rc = ensure_slots(c, 0, pinned ? 0 : n * (in_b + out_b))) return rc;
-    const uint8_t* src = data;
-    uint8_t* dst = out;
-    if (!pinned) {
-      par_memcpy(c, c->h_slot[0], data, n * in_b);
-      src = c->h_slot[0];
-      dst = c->h_slot[0] + n * in_b;
+int run_staged(memo_ec_ctx* c, stage::Plan& pl, bool pinned, bool zc, bool status, size_t scratch,
+               Run run) {
+  const stage::Sizes sz = pl.layout(pinned);
+  // wave w's `dir` extents between the caller's memory and host slot h
+  auto bounce = [&](size_t w, uint8_t* h, stage::Dir dir) {
+    for (size_t i = pl.first[w]; i < pl.first[w + 1]; ++i) {
+      const stage::Extent& e = pl.ext[i];
+      if (e.dir != dir || !e.bytes || e.hat == stage::kNone) continue;
+      if (dir == stage::kIn) par_memcpy(c, h + e.hat, e.host, e.bytes);
+      else par_memcpy(c, e.host, h + e.hat, e.bytes);
     }
-    if (int rc = run(src, dst, n, c->sk)) return rc;
+  };
+  if (zc) {
+    if (int rc = ensure_slots(c, 0, sz.host + (status ? 64 : 0))) return rc;
+    if (int rc = ensure_tabs(c, scratch)) return rc;
+    uint8_t* h = c->h_slot[0];
+    uint32_t* h_st = status ? reinterpret_cast<uint32_t*>(h + ((sz.host + 3) & ~(size_t)3)) : nullptr;
+    if (h_st) *h_st = 0;
+    bounce(0, h, stage::kIn);
+    const StageView v{pl.ext.data(), true, h, reinterpret_cast<uint8_t*>(c->d_tabs), h_st};
+    if (int rc = run(0, v, c->sk)) return rc;
     HIPCHK(hipStreamSynchronize(c->sk));
-    if (!pinned) par_memcpy(c, out, dst, n * out_b);
-    return MEMO_EC_OK;
+    bounce(0, h, stage::kOut);
+    return status ? deferred_rc(c, __atomic_load_n(h_st, __ATOMIC_ACQUIRE)) : MEMO_EC_OK;
   }
-  size_t nb = std::max<size_t>(1, c->opt.pipe_bytes / in_b);
-  nb = std::min(nb, n);
-  if (int rc = ensure_slots(c, nb * (in_b + out_b), pinned ? 0 : nb * (in_b + out_b))) return rc;
-  // slot layout (device and pageable bounce): [in nb*in_b | out nb*out_b]
-  return run_pipeline(
-      c, n, nb,
-      [&](int s, size_t b0, size_t cnt, hipStream_t st) -> int {
-        const uint8_t* src = data + b0 * in_b;
-        if (!pinned) {
-          par_memcpy(c, c->h_slot[s], src, cnt * in_b);
-          src = c->h_slot[s];
+  if (int rc = ensure_slots(c, sz.dev, sz.host)) return rc;
+  if (int rc = ensure_tabs(c, kSlots * scratch)) return rc;
+  // DMA of wave w's `dir` extents between device slot s and the host slot or
+  // a pinned caller's buffers.  Extents adjacent in both slots move as one
+  // copy (a pageable wave's inputs; its outputs; its kSlot bytes); a pinned
+  // caller's buffers are copied one by one, as they may be allocations of
+  // their own even where they lie next to each other.
+  auto dma = [&](size_t w, int s, stage::Dir dir, hipStream_t st) -> int {
+    uint8_t *d0 = nullptr, *p0 = nullptr;
+    size_t len = 0;
+    bool in_slot = false;  // the open copy's host side is the host slot
+    auto flush = [&]() -> int {
+      if (!len) return MEMO_EC_OK;
+      const hipError_t e = dir == stage::kIn ? hipMemcpyAsync(d0, p0, len, hipMemcpyHostToDevice, st)
+                                             : hipMemcpyAsync(p0, d0, len, hipMemcpyDeviceToHost, st);
+      len = 0;
+      return hip_rc(e);
+    };
+    for (stage::Via via : {stage::kCaller, stage::kSlot})
+      for (size_t i = pl.first[w]; i < pl.first[w + 1]; ++i) {
+        const stage::Extent& e = pl.ext[i];
+        if (e.dir != dir || e.via != via || !e.bytes) continue;
+        uint8_t* d = c->d_slot[s] + e.at;
+        const bool slot = e.hat != stage::kNone;
+        uint8_t* p = slot ? c->h_slot[s] + e.hat : static_cast<uint8_t*>(e.host);
+        if (len && slot && in_slot && d == d0 + len && p == p0 + len) {
+          len += e.bytes;
+          continue;
         }
-        return hip_rc(hipMemcpyAsync(c->d_slot[s], src, cnt * in_b, hipMemcpyHostToDevice, st));
+        if (int rc = flush()) return rc;
+        d0 = d;
+        p0 = p;
+        len = e.bytes;
+        in_slot = slot;
+      }
+    return flush();
+  };
+  const size_t nw = pl.waves();
+  const int rc = run_waves(
+      c, nw,
+      [&](int s, size_t w, hipStream_t st) -> int {
+        bounce(w, c->h_slot[s], stage::kIn);
+        return dma(w, s, stage::kIn, st);
       },
-      [&](int s, size_t, size_t cnt, hipStream_t st) -> int {
-        return run(c->d_slot[s], c->d_slot[s] + nb * in_b, cnt, st);
+      [&](int s, size_t w, hipStream_t st) -> int {
+        const StageView v{pl.ext.data() + pl.first[w], false, c->d_slot[s],
+                          reinterpret_cast<uint8_t*>(c->d_tabs) + (size_t)s * scratch,
+                          c->d_status + kStatusPipeline};
+        return run(w, v, st);
       },
-      [&](int s, size_t b0, size_t cnt, hipStream_t st) -> int {
-        uint8_t* dst = pinned ? out + b0 * out_b : c->h_slot[s] + nb * in_b;
-        return hip_rc(hipMemcpyAsync(dst, c->d_slot[s] + nb * in_b, cnt * out_b,
-                                     hipMemcpyDeviceToHost, st));
+      [&](int s, size_t w, hipStream_t st) -> int {
+        if (int rc = dma(w, s, stage::kOut, st)) return rc;
+        // the deferred-error word rides behind the last wave's output, so
+        // reading it costs no extra round trip
+        if (status && w + 1 == nw)
+          HIPCHK(hipMemcpyAsync(c->h_status, c->d_status + kStatusPipeline, sizeof(uint32_t),
+                                hipMemcpyDeviceToHost, st));
+        return MEMO_EC_OK;
       },
-      [&](int s, size_t b0, size_t cnt) {
-        if (!pinned) par_memcpy(c, out + b0 * out_b, c->h_slot[s] + nb * in_b, cnt * out_b);
-      });
+      [&](int s, size_t w) { bounce(w, c->h_slot[s], stage::kOut); });
+  if (rc || !status) return rc;
+  const uint32_t st = *c->h_status;
+  if (st) {
+    HIPCHK(hipMemsetAsync(c->d_status + kStatusPipeline, 0, sizeof(uint32_t), c->sd));
+    HIPCHK(hipStreamSynchronize(c->sd));
+  }
+  return deferred_rc(c, st);
 }
 
-// Host-memory verify through the copy pipeline: each wave's data and parity
-// go to one device slot [data nb*k*S | parity nb*m*S | verdict nb words], the
-// verify and locate run there, and the wave's verdict words come back to
-// their offset in the caller's array.
-int verify_host(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const uint8_t* data,
-                const uint8_t* parity, uint32_t* verdict, bool pinned) {
-  const size_t d_b = (size_t)k * S, p_b = (size_t)m * S, v_b = sizeof(uint32_t);
-  size_t nb = std::max<size_t>(1, c->opt.pipe_bytes / (d_b + p_b));
-  nb = std::min(nb, n);
-  const size_t slot = nb * (d_b + p_b + v_b);
-  if (int rc = ensure_slots(c, slot, pinned ? 0 : slot)) return rc;
-  const size_t p_off = nb * d_b, v_off = nb * (d_b + p_b);
-  return run_pipeline(
-      c, n, nb,
-      [&](int s, size_t b0, size_t cnt, hipStream_t st) -> int {
-        const uint8_t* ds = data + b0 * d_b;
-        const uint8_t* ps = parity + b0 * p_b;
-        if (!pinned) {
-          par_memcpy(c, c->h_slot[s], ds, cnt * d_b);
-          par_memcpy(c, c->h_slot[s] + p_off, ps, cnt * p_b);
-          ds = c->h_slot[s];
-          ps = c->h_slot[s] + p_off;
-        }
-        if (int rc = hip_rc(hipMemcpyAsync(c->d_slot[s], ds, cnt * d_b, hipMemcpyHostToDevice, st)))
-          return rc;
-        return hip_rc(hipMemcpyAsync(c->d_slot[s] + p_off, ps, cnt * p_b, hipMemcpyHostToDevice, st));
-      },
-      [&](int s, size_t, size_t cnt, hipStream_t st) -> int {
-        return verify_device(c, k, m, S, cnt, c->d_slot[s], c->d_slot[s] + p_off,
-                             reinterpret_cast<uint32_t*>(c->d_slot[s] + v_off), st);
-      },
-      [&](int s, size_t b0, size_t cnt, hipStream_t st) -> int {
-        void* dst = pinned ? static_cast<void*>(verdict + b0) : c->h_slot[s] + v_off;
-        return hip_rc(hipMemcpyAsync(dst, c->d_slot[s] + v_off, cnt * v_b, hipMemcpyDeviceToHost, st));
-      },
-      [&](int s, size_t b0, size_t cnt) {
-        if (!pinned) std::memcpy(verdict + b0, c->h_slot[s] + v_off, cnt * v_b);
-      });
+// Host-memory encode of n blocks, block b of size(b)-byte shards at off(b)
+// (uniform calls: S and b * S; ragged ones: the call's arrays).
+// launch(blocks, src, dst, st) enqueues the encode of one wave's blocks.
+template <class Size, class Off, class Launch>
+int encode_host(memo_ec_ctx* c, int k, int m, size_t n, Size size, Off off, const uint8_t* data,
+                uint8_t* parity, bool pinned, Launch launch) {
+  const bool zc = zero_copy(c, (size_t)(k + m) * off(n));
+  const std::vector<ragged::Range> waves = call_waves(c, zc, n, (uint64_t)k, size);
+  stage::Plan pl(waves.size(), 2 * waves.size());
+  for (const ragged::Range& w : waves) {
+    pl.add_blocks(w, off, data, (uint64_t)k, stage::kIn);
+    pl.add_blocks(w, off, parity, (uint64_t)m, stage::kOut);
+    pl.end_wave();
+  }
+  return run_staged(c, pl, pinned, zc, false, 0, [&](size_t w, const StageView& v, hipStream_t st) {
+    return launch(waves[w], v(0), v(1), st);
+  });
 }
 
-// Host-memory ragged encode: zero-copy on pinned memory for small calls,
-// else the copy pipeline with waves cut on block boundaries by input bytes
-// (host_mac with its fixed block size replaced by the call's offsets).
-int encode_ragged_host(memo_ec_ctx* c, int k, int m, size_t n, const size_t* sizes,
-                       const uint64_t* off, const uint8_t* data, uint8_t* parity, bool pinned) {
-  const uint64_t T = off[n];
-  const size_t in_b = (size_t)k * T, out_b = (size_t)m * T;
-  if (in_b + out_b <= zc_max_bytes(c)) {
-    if (int rc = ensure_slots(c, 0, pinned ? 0 : in_b + out_b)) return rc;
-    const uint8_t* src = data;
-    uint8_t* dst = parity;
-    if (!pinned) {
-      par_memcpy(c, c->h_slot[0], data, in_b);
-      src = c->h_slot[0];
-      dst = c->h_slot[0] + in_b;
-    }
-    if (int rc = ragged_device(c, k, m, n, sizes, off, src, dst, nullptr, c->sk)) return rc;
-    HIPCHK(hipStreamSynchronize(c->sk));
-    if (!pinned) par_memcpy(c, parity, dst, out_b);
-    return MEMO_EC_OK;
+// Host-memory verify, as encode_host: each wave's data and parity go in, its
+// verdict words come back to their place in the caller's array.  Always
+// through the copy pipeline: no verify runs zero-copy.
+template <class Size, class Off, class Launch>
+int verify_host(memo_ec_ctx* c, int k, int m, size_t n, Size size, Off off, const uint8_t* data,
+                const uint8_t* parity, uint32_t* verdict, bool pinned, Launch launch) {
+  const std::vector<ragged::Range> waves = call_waves(c, false, n, (uint64_t)(k + m), size);
+  stage::Plan pl(waves.size(), 3 * waves.size());
+  for (const ragged::Range& w : waves) {
+    pl.add_blocks(w, off, data, (uint64_t)k, stage::kIn);
+    pl.add_blocks(w, off, parity, (uint64_t)m, stage::kIn);
+    pl.add(verdict + w.b0, (w.b1 - w.b0) * sizeof(uint32_t), stage::kOut);
+    pl.end_wave();
   }
-  const std::vector<ragged::Range> waves = ragged::cut_waves(sizes, n, (uint64_t)k, c->opt.pipe_bytes);
-  uint64_t tmax = 0;
-  for (const auto& w : waves) tmax = std::max<uint64_t>(tmax, off[w.b1] - off[w.b0]);
-  const size_t slot = (size_t)(k + m) * tmax, o_off = (size_t)k * tmax;
-  if (int rc = ensure_slots(c, slot, pinned ? 0 : slot)) return rc;
-  auto wt = [&](size_t w) { return off[waves[w].b1] - off[waves[w].b0]; };
-  return run_waves(
-      c, waves.size(),
-      [&](int s, size_t w, hipStream_t st) -> int {
-        const size_t nb = (size_t)k * wt(w);
-        if (!nb) return MEMO_EC_OK;
-        const uint8_t* src = data + (size_t)k * off[waves[w].b0];
-        if (!pinned) {
-          par_memcpy(c, c->h_slot[s], src, nb);
-          src = c->h_slot[s];
-        }
-        return hip_rc(hipMemcpyAsync(c->d_slot[s], src, nb, hipMemcpyHostToDevice, st));
-      },
-      [&](int s, size_t w, hipStream_t st) -> int {
-        const ragged::Range& r = waves[w];
-        return ragged_device(c, k, m, r.b1 - r.b0, sizes + r.b0, off + r.b0, c->d_slot[s],
-                             c->d_slot[s] + o_off, nullptr, st);
-      },
-      [&](int s, size_t w, hipStream_t st) -> int {
-        const size_t nb = (size_t)m * wt(w);
-        if (!nb) return MEMO_EC_OK;
-        uint8_t* dst = pinned ? parity + (size_t)m * off[waves[w].b0] : c->h_slot[s] + o_off;
-        return hip_rc(hipMemcpyAsync(dst, c->d_slot[s] + o_off, nb, hipMemcpyDeviceToHost, st));
-      },
-      [&](int s, size_t w) {
-        if (!pinned)
-          par_memcpy(c, parity + (size_t)m * off[waves[w].b0], c->h_slot[s] + o_off, (size_t)m * wt(w));
-      });
-}
-
-// Host-memory ragged verify through the copy pipeline (verify_host's slot
-// layout: [data | parity | verdict words], sized by the largest wave).
-int verify_ragged_host(memo_ec_ctx* c, int k, int m, size_t n, const size_t* sizes,
-                       const uint64_t* off, const uint8_t* data, const uint8_t* parity,
-                       uint32_t* verdict, bool pinned) {
-  const std::vector<ragged::Range> waves =
-      ragged::cut_waves(sizes, n, (uint64_t)(k + m), c->opt.pipe_bytes);
-  uint64_t tmax = 0;
-  size_t nmax = 0;
-  for (const auto& w : waves) {
-    tmax = std::max<uint64_t>(tmax, off[w.b1] - off[w.b0]);
-    nmax = std::max(nmax, w.b1 - w.b0);
-  }
-  const size_t p_off = (size_t)k * tmax, v_off = (size_t)(k + m) * tmax, v_b = sizeof(uint32_t);
-  const size_t slot = v_off + nmax * v_b;
-  if (int rc = ensure_slots(c, slot, pinned ? 0 : slot)) return rc;
-  auto wt = [&](size_t w) { return off[waves[w].b1] - off[waves[w].b0]; };
-  return run_waves(
-      c, waves.size(),
-      [&](int s, size_t w, hipStream_t st) -> int {
-        const size_t db = (size_t)k * wt(w), pb = (size_t)m * wt(w);
-        if (!db) return MEMO_EC_OK;
-        const uint8_t* ds = data + (size_t)k * off[waves[w].b0];
-        const uint8_t* ps = parity + (size_t)m * off[waves[w].b0];
-        if (!pinned) {
-          par_memcpy(c, c->h_slot[s], ds, db);
-          par_memcpy(c, c->h_slot[s] + p_off, ps, pb);
-          ds = c->h_slot[s];
-          ps = c->h_slot[s] + p_off;
-        }
-        if (int rc = hip_rc(hipMemcpyAsync(c->d_slot[s], ds, db, hipMemcpyHostToDevice, st))) return rc;
-        return hip_rc(hipMemcpyAsync(c->d_slot[s] + p_off, ps, pb, hipMemcpyHostToDevice, st));
-      },
-      [&](int s, size_t w, hipStream_t st) -> int {
-        const ragged::Range& r = waves[w];
-        return ragged_device(c, k, m, r.b1 - r.b0, sizes + r.b0, off + r.b0, c->d_slot[s],
-                             c->d_slot[s] + p_off, reinterpret_cast<uint32_t*>(c->d_slot[s] + v_off), st);
-      },
-      [&](int s, size_t w, hipStream_t st) -> int {
-        const ragged::Range& r = waves[w];
-        void* dst = pinned ? static_cast<void*>(verdict + r.b0) : c->h_slot[s] + v_off;
-        return hip_rc(hipMemcpyAsync(dst, c->d_slot[s] + v_off, (r.b1 - r.b0) * v_b,
-                                     hipMemcpyDeviceToHost, st));
-      },
-      [&](int s, size_t w) {
-        const ragged::Range& r = waves[w];
-        if (!pinned) std::memcpy(verdict + r.b0, c->h_slot[s] + v_off, (r.b1 - r.b0) * v_b);
-      });
+  return run_staged(c, pl, pinned, false, false, 0, [&](size_t w, const StageView& v, hipStream_t st) {
+    return launch(waves[w], v(0), v(1), reinterpret_cast<uint32_t*>(v(2)), st);
+  });
 }
 
 // Decode rows of one erasure pattern on the host: row r = C[lost_r] *
@@ -1513,15 +1534,6 @@ int launch_rebuild_pieces(memo_ec_ctx* c, const std::vector<RPiece>& ps, uint8_t
   return MEMO_EC_OK;
 }
 
-// What a call reports once its work is done: the ctx's deferred error, else
-// ESINGULAR when its status word `st` has the singular bit.
-int deferred_rc(memo_ec_ctx* ctx, uint32_t st) {
-  int rc = ctx->deferred;
-  ctx->deferred = 0;
-  if (rc == MEMO_EC_OK && (st & 1u)) rc = MEMO_EC_ESINGULAR;
-  return rc;
-}
-
 int take_deferred(memo_ec_ctx* ctx) {
   uint32_t st = 0;
   HIPCHK(hipMemcpy(&st, ctx->d_status, sizeof st, hipMemcpyDeviceToHost));
@@ -1553,188 +1565,67 @@ int rebuild_segments_impl(memo_ec_ctx* c, int nseg, const memo_ec_rebuild_segmen
   }
   if (where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
   const bool pinned = where == MEMO_EC_HOST_PINNED;
-  if (per_block) {
-    // device rebuilds still pending on the ctx stream read the same scratch
-    const hipError_t q = hipEventQuery(c->ev_order);
-    if (q == hipErrorNotReady) {
-      HIPCHK(hipStreamWaitEvent(c->sk, c->ev_order, 0));
-    } else if (q != hipSuccess) {
-      return hip_rc(q);
-    }
-  }
-  // Chunks of at most one pipeline batch of survivors, packed in order into
-  // waves of at most one batch; a wave's slot holds [survivors | outputs |
-  // per-block indices].
-  struct Chunk {
-    RPiece p;  // host pointers
-    size_t in, out, idx;
-    size_t o_in = 0, o_out = 0, o_idx = 0;
-  };
-  std::vector<Chunk> ch;
-  const size_t pipe = c->opt.pipe_bytes;
+  if (per_block)
+    if (int rc = wait_device_rebuilds(c)) return rc;
+  // Chunks (pieces with host pointers) of at most one pipeline batch of
+  // survivors, packed in order into waves of at most one batch.
+  std::vector<RPiece> ch;
   size_t total = 0;
   for (const RPiece& p : ps) {
     const size_t in_b = (size_t)p.k * p.S, out_b = (size_t)p.e * p.S;
     const bool uni = p.mode == MAC_ENCODE;
-    const size_t per = std::max<size_t>(1, pipe / in_b);
+    const size_t per = std::max<size_t>(1, c->opt.pipe_bytes / in_b);
     for (size_t b0 = 0; b0 < p.n; b0 += per) {
-      Chunk x;
-      x.p = p;
-      x.p.b0 = b0;
-      x.p.n = std::min(per, p.n - b0);
-      x.p.surv = p.surv + b0 * in_b;
-      x.p.out = p.out + b0 * out_b;
+      RPiece x = p;
+      x.b0 = b0;
+      x.n = std::min(per, p.n - b0);
+      x.surv = p.surv + b0 * in_b;
+      x.out = p.out + b0 * out_b;
       if (!uni) {
-        x.p.sidx = p.sidx + b0 * (size_t)p.k;
-        x.p.lidx = p.lidx + b0 * (size_t)p.e;
+        x.sidx = p.sidx + b0 * (size_t)p.k;
+        x.lidx = p.lidx + b0 * (size_t)p.e;
       }
-      x.in = x.p.n * in_b;
-      x.out = x.p.n * out_b;
-      x.idx = uni ? 0 : x.p.n * (size_t)(p.k + p.e);
-      total += x.in + x.out + x.idx;
+      total += x.n * (in_b + out_b + (uni ? 0 : (size_t)(p.k + p.e)));
       ch.push_back(x);
     }
   }
-  struct Wave {
-    std::vector<size_t> ids;
-    size_t in = 0, out = 0, idx = 0;
-  };
-  std::vector<Wave> waves;
-  // zero-copy (one wave, whatever its size): the call's survivors, outputs
-  // and per-block indices plus the status word's 64 bytes within the bound
-  const bool zc = total + 64 <= zc_max_bytes(c);
-  for (size_t i = 0; i < ch.size(); ++i) {
-    if (waves.empty() || (!zc && waves.back().in + ch[i].in > pipe)) waves.emplace_back();
-    Wave& w = waves.back();
-    w.ids.push_back(i);
-    w.in += ch[i].in;
-    w.out += ch[i].out;
-    w.idx += ch[i].idx;
-  }
-  // pinned: the survivors and outputs stay in (zero-copy) or move by DMA
-  // from (pipeline) the caller's buffers, so the host slot holds a wave's
-  // indices only (and behind them the zero-copy status word) -- no pinned
-  // bounce buffers of the payload's size
-  auto h_idx = [&](const Wave& w, uint8_t* h) { return h + (pinned ? 0 : w.in + w.out); };
-  size_t slot = 0, hslot = 0, rows = 0;
-  for (Wave& w : waves) {
-    size_t oi = 0, oo = w.in, ox = 0;
-    for (size_t i : w.ids) {
-      ch[i].o_in = oi;
-      ch[i].o_out = oo;
-      ch[i].o_idx = ox;  // within the wave's indices
-      oi += ch[i].in;
-      oo += ch[i].out;
-      ox += ch[i].idx;
-    }
-    slot = std::max(slot, w.in + w.out + w.idx);
-    hslot = std::max(hslot, pinned ? w.idx : w.in + w.out + w.idx);
-    std::vector<RPiece> wp;
-    for (size_t i : w.ids) wp.push_back(ch[i].p);
-    rows = std::max(rows, rows_scratch(wp));  // decode rows + table images (256-byte multiple)
-  }
-  // the pieces as the kernels see them: the wave's indices at idx, survivors
-  // and outputs in slot memory at base or (pinned_io) in the caller's buffers
-  auto staged = [&](const Wave& w, uint8_t* base, const uint8_t* idx, bool pinned_io) {
-    std::vector<RPiece> dp;
-    for (size_t i : w.ids) {
-      RPiece p = ch[i].p;
-      if (!pinned_io) {
-        p.surv = base + ch[i].o_in;
-        p.out = base + ch[i].o_out;
-      }
-      if (p.mode != MAC_ENCODE) {
-        p.sidx = idx + ch[i].o_idx;
-        p.lidx = p.sidx + p.n * (size_t)p.k;
-      }
-      dp.push_back(p);
-    }
-    return dp;
-  };
-  auto stage_idx = [&](const Wave& w, uint8_t* idx) {
-    for (size_t i : w.ids) {
-      const RPiece& p = ch[i].p;
+  // zero-copy: the call's survivors, outputs and per-block indices plus the
+  // status word's 64 bytes within the bound
+  const bool zc = zero_copy(c, total + 64);
+  const std::vector<ragged::Range> waves =
+      call_waves(c, zc, ch.size(), 1, [&](size_t i) { return ch[i].n * (size_t)ch[i].k * ch[i].S; });
+  // a wave's extents, per chunk: survivors, outputs and (per-block patterns)
+  // the two index arrays, which the library stages
+  stage::Plan pl(waves.size(), 4 * ch.size());
+  size_t rows = 0;
+  for (const ragged::Range& w : waves) {
+    for (size_t i = w.b0; i < w.b1; ++i) {
+      const RPiece& p = ch[i];
+      pl.add(p.surv, p.n * (size_t)p.k * p.S, stage::kIn);
+      pl.add(p.out, p.n * (size_t)p.e * p.S, stage::kOut);
       if (p.mode == MAC_ENCODE) continue;
-      std::memcpy(idx + ch[i].o_idx, p.sidx, p.n * (size_t)p.k);
-      std::memcpy(idx + ch[i].o_idx + p.n * (size_t)p.k, p.lidx, p.n * (size_t)p.e);
+      pl.add(p.sidx, p.n * (size_t)p.k, stage::kIn, stage::kSlot);
+      pl.add(p.lidx, p.n * (size_t)p.e, stage::kIn, stage::kSlot);
     }
-  };
-  if (zc) {
-    // Small call: the kernels read the survivors and indices from, and
-    // write their output to, pinned host memory (no DMA copies); the status
-    // word rides in the slot.
-    const Wave& w = waves[0];
-    if (int rc = ensure_slots(c, 0, hslot + 64)) return rc;
-    if (int rc = ensure_tabs(c, rows)) return rc;
-    uint8_t* h = c->h_slot[0];
-    uint32_t* h_st = reinterpret_cast<uint32_t*>(h + ((hslot + 3) & ~(size_t)3));
-    *h_st = 0;
-    stage_idx(w, h_idx(w, h));
-    if (!pinned)
-      for (size_t i : w.ids) par_memcpy(c, h + ch[i].o_in, ch[i].p.surv, ch[i].in);
-    if (int rc = launch_rebuild_pieces(c, staged(w, h, h_idx(w, h), pinned),
-                                       reinterpret_cast<uint8_t*>(c->d_tabs), c->sk, h_st))
-      return rc;
-    HIPCHK(hipStreamSynchronize(c->sk));
-    if (!pinned)
-      for (size_t i : w.ids) par_memcpy(c, ch[i].p.out, h + ch[i].o_out, ch[i].out);
-    return deferred_rc(c, __atomic_load_n(h_st, __ATOMIC_ACQUIRE));
+    pl.end_wave();
+    // decode rows + table images (256-byte multiple)
+    rows = std::max(rows, rows_scratch(std::vector<RPiece>(ch.begin() + w.b0, ch.begin() + w.b1)));
   }
-  if (int rc = ensure_slots(c, slot, hslot)) return rc;
-  if (int rc = ensure_tabs(c, kSlots * rows)) return rc;
-  const int rc = run_waves(
-      c, waves.size(),
-      [&](int s, size_t wi, hipStream_t st) -> int {
-        const Wave& w = waves[wi];
-        uint8_t* h = c->h_slot[s];
-        uint8_t* d = c->d_slot[s];
-        stage_idx(w, h_idx(w, h));
-        if (w.idx)
-          HIPCHK(hipMemcpyAsync(d + w.in + w.out, h_idx(w, h), w.idx, hipMemcpyHostToDevice, st));
-        for (size_t i : w.ids) {
-          if (pinned) {
-            HIPCHK(hipMemcpyAsync(d + ch[i].o_in, ch[i].p.surv, ch[i].in, hipMemcpyHostToDevice, st));
-          } else {
-            par_memcpy(c, h + ch[i].o_in, ch[i].p.surv, ch[i].in);
-          }
-        }
-        if (!pinned) HIPCHK(hipMemcpyAsync(d, h, w.in, hipMemcpyHostToDevice, st));
-        return MEMO_EC_OK;
-      },
-      [&](int s, size_t wi, hipStream_t st) -> int {
-        const Wave& w = waves[wi];
-        uint8_t* d = c->d_slot[s];
-        return launch_rebuild_pieces(c, staged(w, d, d + w.in + w.out, false),
-                                     reinterpret_cast<uint8_t*>(c->d_tabs) + (size_t)s * rows, st,
-                                     c->d_status + kStatusPipeline);
-      },
-      [&](int s, size_t wi, hipStream_t st) -> int {
-        const Wave& w = waves[wi];
-        uint8_t* d = c->d_slot[s];
-        if (pinned) {
-          for (size_t i : w.ids)
-            HIPCHK(hipMemcpyAsync(ch[i].p.out, d + ch[i].o_out, ch[i].out, hipMemcpyDeviceToHost, st));
-        } else {
-          HIPCHK(hipMemcpyAsync(c->h_slot[s] + w.in, d + w.in, w.out, hipMemcpyDeviceToHost, st));
-        }
-        // the deferred-error word rides behind the last wave's output, so
-        // reading it costs no extra round trip
-        if (wi + 1 == waves.size())
-          HIPCHK(hipMemcpyAsync(c->h_status, c->d_status + kStatusPipeline, sizeof(uint32_t),
-                                hipMemcpyDeviceToHost, st));
-        return MEMO_EC_OK;
-      },
-      [&](int s, size_t wi) {
-        if (pinned) return;
-        for (size_t i : waves[wi].ids) par_memcpy(c, ch[i].p.out, c->h_slot[s] + ch[i].o_out, ch[i].out);
-      });
-  if (rc) return rc;
-  const uint32_t st = *c->h_status;
-  if (st) {
-    HIPCHK(hipMemsetAsync(c->d_status + kStatusPipeline, 0, sizeof(uint32_t), c->sd));
-    HIPCHK(hipStreamSynchronize(c->sd));
-  }
-  return deferred_rc(c, st);
+  return run_staged(c, pl, pinned, zc, true, rows, [&](size_t w, const StageView& v, hipStream_t st) {
+    // the wave's pieces as the kernels see them
+    std::vector<RPiece> dp(ch.begin() + waves[w].b0, ch.begin() + waves[w].b1);
+    size_t x = 0;
+    for (RPiece& p : dp) {
+      p.surv = v(x);
+      p.out = v(x + 1);
+      x += 2;
+      if (p.mode == MAC_ENCODE) continue;
+      p.sidx = v(x);
+      p.lidx = v(x + 1);
+      x += 2;
+    }
+    return launch_rebuild_pieces(c, dp, v.scratch, st, v.status);
+  });
 }
 
 // ---- Ragged rebuild (memo_ec_rebuild_ragged).
@@ -1768,80 +1659,48 @@ int ragged_rows_device(memo_ec_ctx* ctx, const RaggedRebuild& rb, size_t n, cons
   const int k = rb.k, e = rb.e, R = rb.R, KC = rb.KC;
   const uint32_t kpad = kpad_of((uint32_t)k, KC);
   const uint32_t cap = ragged_rows_cap(R, kpad);
-  uint64_t limit = 0x7fffffffull - MAC_TILE;
-  if (ctx->opt.max_launch_tiles >= 1 && ctx->opt.max_launch_tiles < limit)
-    limit = ctx->opt.max_launch_tiles;
-  const std::vector<ragged::Range> spans = ragged::cut_rows_spans(sizes, n, cap, limit);
-  // buffer layout: [surv_idx n x k | lost_idx n x e: idx_host] then per span
-  // [coff | desc | orig]
-  struct SpanAt {
-    ragged::Counts cnt;
-    size_t coff, desc, orig;
-  };
-  std::vector<SpanAt> at(spans.size());
-  const size_t sidx_b = n * (size_t)k, lidx_b = n * (size_t)e;
-  size_t bytes = rb.idx_host ? round16(sidx_b + lidx_b) : 0;
-  for (size_t i = 0; i < spans.size(); ++i) {
-    SpanAt& a = at[i];
-    a.cnt = ragged::rows_index_counts(sizes + spans[i].b0, spans[i].b1 - spans[i].b0, cap);
-    a.coff = bytes;
-    bytes += round16((a.cnt.nq + 1) * sizeof(uint64_t));
-    a.desc = bytes;
-    bytes += a.cnt.tiles * sizeof(ragged::RowsTileDesc);
-    a.orig = bytes;
-    bytes += round16(a.cnt.nq * sizeof(uint32_t));
-  }
   const uint32_t* lw0 = nullptr;
   if (int rc = lw0_table(ctx, k, rb.m, &lw0)) return rc;
-  memo_ec_ctx::IdxBuf* buf = nullptr;
-  if (int rc = idx_acquire(ctx, bytes, &buf)) return rc;
-  const uint8_t* sidx = rb.sidx;
-  const uint8_t* lidx = rb.lidx;
-  if (rb.idx_host) {
-    std::memcpy(buf->host, rb.sidx, sidx_b);
-    std::memcpy(buf->host + sidx_b, rb.lidx, lidx_b);
-    sidx = buf->dev;
-    lidx = buf->dev + sidx_b;
-  }
-  for (size_t i = 0; i < spans.size(); ++i)
-    ragged::build_rows_index(sizes + spans[i].b0, spans[i].b1 - spans[i].b0, cap,
-                             reinterpret_cast<uint64_t*>(buf->host + at[i].coff),
-                             reinterpret_cast<uint32_t*>(buf->host + at[i].orig),
-                             reinterpret_cast<ragged::RowsTileDesc*>(buf->host + at[i].desc));
-  buf->used = true;  // from here the buffer belongs to the enqueued work
-  int rc = bytes ? hip_rc(hipMemcpyAsync(buf->dev, buf->host, bytes, hipMemcpyHostToDevice, st))
-                 : MEMO_EC_OK;
-  if (!rc) {
-    const DecodeArgs a = decode_args(ctx, k, rb.m, e, n, sidx, lidx, rb.rows, rb.status, lw0);
-    rc = hip_rc(launch_decode_coef(a, st));
-  }
-  const size_t per = (size_t)R * kpad;
-  for (size_t i = 0; i < spans.size() && !rc; ++i) {
-    if (at[i].cnt.tiles == 0) continue;
-    const uint64_t o = off[spans[i].b0] - off[0];
-    RaggedLaunch L{};
-    MacSeg& s = L.seg;
-    s.in = surv + (uint64_t)k * o;
-    s.out = out + (uint64_t)e * o;
-    s.coef = rb.rows + spans[i].b0 * (size_t)e * k;
-    s.coef_bstride = (uint64_t)e * k;
-    s.coef_rows = (uint32_t)e;
-    s.coef_dense = 0;
-    s.lo_dw = (uint32_t)(cap * (per + 1) * 4);
-    s.n = at[i].cnt.nq;
-    s.tiles = at[i].cnt.tiles;
-    s.kin = (uint32_t)k;
-    s.r = (uint32_t)e;
-    s.kpad = kpad;
-    s.flat = 1;
-    L.idx.coff = reinterpret_cast<const uint64_t*>(buf->dev + at[i].coff);
-    L.idx.orig = reinterpret_cast<const uint32_t*>(buf->dev + at[i].orig);
-    L.idx.desc = reinterpret_cast<const uint4*>(buf->dev + at[i].desc);
-    L.xcd = s.tiles >= ctx->opt.xcd_min_tiles ? 1u : 0u;
-    rc = hip_rc(launch_mac_ragged_rows(KC, R, L, (uint32_t)s.tiles, cap * (per + 1) * 20, st));
-  }
-  const int rc2 = hip_rc(hipEventRecord(buf->ev, st));
-  return rc ? rc : rc2;
+  // idx_host: the pattern bytes [surv_idx n x k | lost_idx n x e] go up as the
+  // index's head
+  const size_t sidx_b = n * (size_t)k, lidx_b = n * (size_t)e;
+  return with_ragged_index(
+      ctx, RowsKind{cap}, sizes, n, rb.idx_host ? sidx_b + lidx_b : 0,
+      [&](uint8_t* host) {
+        if (!rb.idx_host) return;
+        std::memcpy(host, rb.sidx, sidx_b);
+        std::memcpy(host + sidx_b, rb.lidx, lidx_b);
+      },
+      st, [&](const uint8_t* head, const std::vector<SpanIdx>& spans) -> int {
+        const DecodeArgs a = decode_args(ctx, k, rb.m, e, n, rb.idx_host ? head : rb.sidx,
+                                         rb.idx_host ? head + sidx_b : rb.lidx, rb.rows, rb.status, lw0);
+        if (int rc = hip_rc(launch_decode_coef(a, st))) return rc;
+        const size_t per = (size_t)R * kpad;
+        for (const SpanIdx& sp : spans) {
+          if (sp.cnt.tiles == 0) continue;
+          const uint64_t o = off[sp.b0] - off[0];
+          RaggedLaunch L{};
+          MacSeg& s = L.seg;
+          s.in = surv + (uint64_t)k * o;
+          s.out = out + (uint64_t)e * o;
+          s.coef = rb.rows + sp.b0 * (size_t)e * k;
+          s.coef_bstride = (uint64_t)e * k;
+          s.coef_rows = (uint32_t)e;
+          s.coef_dense = 0;
+          s.lo_dw = (uint32_t)(cap * (per + 1) * 4);
+          s.n = sp.cnt.nq;
+          s.tiles = sp.cnt.tiles;
+          s.kin = (uint32_t)k;
+          s.r = (uint32_t)e;
+          s.kpad = kpad;
+          s.flat = 1;
+          L.idx = sp.idx;
+          L.xcd = s.tiles >= ctx->opt.xcd_min_tiles ? 1u : 0u;
+          if (int rc = hip_rc(launch_mac_ragged_rows(KC, R, L, (uint32_t)s.tiles, cap * (per + 1) * 20, st)))
+            return rc;
+        }
+        return MEMO_EC_OK;
+      });
 }
 
 int ragged_rebuild_device(memo_ec_ctx* ctx, const RaggedRebuild& rb, size_t n, const size_t* sizes,
@@ -1855,110 +1714,43 @@ size_t ragged_rows_bytes(const RaggedRebuild& rb, size_t n) {
   return rb.tab ? 0 : round256(n * (size_t)rb.e * rb.k);
 }
 
-// Host-memory ragged rebuild: zero-copy on pinned memory for small calls,
-// else the copy pipeline with waves cut on block boundaries by the bytes a
-// block moves ((k + e) * S[b]); each wave's pattern bytes go up with its
-// index.  The singular word rides in the zero-copy slot, or comes back
-// behind the last wave's output (as rebuild_segments_impl's).
+// Host-memory ragged rebuild: the ragged encode's extents with waves cut by
+// the bytes a block moves ((k + e) * S[b]); each wave's pattern bytes go up
+// with its index (idx_host), its decode rows have the wave's own part of the
+// scratch, and the call reports the singular word.
 int rebuild_ragged_host(memo_ec_ctx* c, RaggedRebuild rb, size_t n, const size_t* sizes,
                         const uint64_t* off, const uint8_t* surv, uint8_t* out, bool pinned) {
   const int k = rb.k, e = rb.e;
   const bool per_block = rb.tab == nullptr;
-  const uint8_t* sidx = rb.sidx;
-  const uint8_t* lidx = rb.lidx;
   rb.idx_host = true;
-  if (per_block) {
-    // device rebuilds still pending on the ctx stream use the same scratch
-    const hipError_t q = hipEventQuery(c->ev_order);
-    if (q == hipErrorNotReady) {
-      HIPCHK(hipStreamWaitEvent(c->sk, c->ev_order, 0));
-    } else if (q != hipSuccess) {
-      return hip_rc(q);
-    }
-  }
-  const uint64_t T = off[n];
-  const size_t in_b = (size_t)k * T, out_b = (size_t)e * T;
+  if (per_block)
+    if (int rc = wait_device_rebuilds(c)) return rc;
   const size_t idx_b = per_block ? n * (size_t)(k + e) : 0;
-  if (in_b + out_b + idx_b + 64 <= zc_max_bytes(c)) {
-    const size_t payload = pinned ? 0 : in_b + out_b;
-    if (int rc = ensure_slots(c, 0, payload + 64)) return rc;
-    if (int rc = ensure_tabs(c, ragged_rows_bytes(rb, n))) return rc;
-    uint8_t* h = c->h_slot[0];
-    uint32_t* h_st = reinterpret_cast<uint32_t*>(h + ((payload + 3) & ~(size_t)3));
-    *h_st = 0;
-    const uint8_t* src = surv;
-    uint8_t* dst = out;
-    if (!pinned) {
-      par_memcpy(c, h, surv, in_b);
-      src = h;
-      dst = h + in_b;
-    }
-    rb.rows = reinterpret_cast<uint8_t*>(c->d_tabs);
-    rb.status = h_st;
-    if (int rc = ragged_rebuild_device(c, rb, n, sizes, off, src, dst, c->sk)) return rc;
-    HIPCHK(hipStreamSynchronize(c->sk));
-    if (!pinned) par_memcpy(c, out, dst, out_b);
-    return deferred_rc(c, __atomic_load_n(h_st, __ATOMIC_ACQUIRE));
-  }
+  const bool zc = zero_copy(c, (size_t)(k + e) * off[n] + idx_b + 64);
   const std::vector<ragged::Range> waves =
-      ragged::cut_waves(sizes, n, (uint64_t)(k + e), c->opt.pipe_bytes);
-  uint64_t tmax = 0;
+      call_waves(c, zc, n, (uint64_t)(k + e), [&](size_t b) { return sizes[b]; });
+  auto at = [&](size_t b) { return off[b]; };
+  stage::Plan pl(waves.size(), 2 * waves.size());
   size_t nmax = 0;
-  for (const auto& w : waves) {
-    tmax = std::max<uint64_t>(tmax, off[w.b1] - off[w.b0]);
+  for (const ragged::Range& w : waves) {
+    pl.add_blocks(w, at, surv, (uint64_t)k, stage::kIn);
+    pl.add_blocks(w, at, out, (uint64_t)e, stage::kOut);
+    pl.end_wave();
     nmax = std::max(nmax, w.b1 - w.b0);
   }
-  const size_t slot = (size_t)(k + e) * tmax, o_off = (size_t)k * tmax;
-  const size_t rows_b = ragged_rows_bytes(rb, nmax);
-  if (int rc = ensure_slots(c, slot, pinned ? 0 : slot)) return rc;
-  if (int rc = ensure_tabs(c, kSlots * rows_b)) return rc;
-  auto wt = [&](size_t w) { return off[waves[w].b1] - off[waves[w].b0]; };
-  const int rc = run_waves(
-      c, waves.size(),
-      [&](int s, size_t w, hipStream_t st) -> int {
-        const size_t nb = (size_t)k * wt(w);
-        if (!nb) return MEMO_EC_OK;
-        const uint8_t* src = surv + (size_t)k * off[waves[w].b0];
-        if (!pinned) {
-          par_memcpy(c, c->h_slot[s], src, nb);
-          src = c->h_slot[s];
-        }
-        return hip_rc(hipMemcpyAsync(c->d_slot[s], src, nb, hipMemcpyHostToDevice, st));
-      },
-      [&](int s, size_t w, hipStream_t st) -> int {
-        const ragged::Range& r = waves[w];
-        RaggedRebuild wb = rb;
-        if (per_block) {
-          wb.sidx = sidx + r.b0 * (size_t)k;
-          wb.lidx = lidx + r.b0 * (size_t)e;
-          wb.rows = reinterpret_cast<uint8_t*>(c->d_tabs) + (size_t)s * rows_b;
-          wb.status = c->d_status + kStatusPipeline;
-        }
-        return ragged_rebuild_device(c, wb, r.b1 - r.b0, sizes + r.b0, off + r.b0, c->d_slot[s],
-                                     c->d_slot[s] + o_off, st);
-      },
-      [&](int s, size_t w, hipStream_t st) -> int {
-        const size_t nb = (size_t)e * wt(w);
-        if (nb) {
-          uint8_t* dst = pinned ? out + (size_t)e * off[waves[w].b0] : c->h_slot[s] + o_off;
-          HIPCHK(hipMemcpyAsync(dst, c->d_slot[s] + o_off, nb, hipMemcpyDeviceToHost, st));
-        }
-        if (w + 1 == waves.size())
-          HIPCHK(hipMemcpyAsync(c->h_status, c->d_status + kStatusPipeline, sizeof(uint32_t),
-                                hipMemcpyDeviceToHost, st));
-        return MEMO_EC_OK;
-      },
-      [&](int s, size_t w) {
-        if (!pinned)
-          par_memcpy(c, out + (size_t)e * off[waves[w].b0], c->h_slot[s] + o_off, (size_t)e * wt(w));
-      });
-  if (rc) return rc;
-  const uint32_t st = *c->h_status;
-  if (st) {
-    HIPCHK(hipMemsetAsync(c->d_status + kStatusPipeline, 0, sizeof(uint32_t), c->sd));
-    HIPCHK(hipStreamSynchronize(c->sd));
-  }
-  return deferred_rc(c, st);
+  return run_staged(c, pl, pinned, zc, true, ragged_rows_bytes(rb, nmax),
+                    [&](size_t w, const StageView& v, hipStream_t st) {
+                      const ragged::Range& r = waves[w];
+                      RaggedRebuild wb = rb;
+                      if (per_block) {
+                        wb.sidx = rb.sidx + r.b0 * (size_t)k;
+                        wb.lidx = rb.lidx + r.b0 * (size_t)e;
+                        wb.rows = v.scratch;
+                        wb.status = v.status;
+                      }
+                      return ragged_rebuild_device(c, wb, r.b1 - r.b0, sizes + r.b0, off + r.b0, v(0),
+                                                   v(1), st);
+                    });
 }
 
 }  // namespace
@@ -2152,12 +1944,11 @@ int memo_ec_encode_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const
   DeviceGuard g(c->device);
   if (where == MEMO_EC_DEVICE) return encode_device(c, k, m, S, n, data, parity, c->stream);
   if (where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
-
-  return host_mac(c, n, (size_t)k * S, (size_t)m * S, data, parity,
-                  where == MEMO_EC_HOST_PINNED,
-                  [&](const uint8_t* src, uint8_t* dst, size_t cnt, hipStream_t st) {
-                    return encode_device(c, k, m, S, cnt, src, dst, st);
-                  });
+  return encode_host(c, k, m, n, [S](size_t) { return S; }, [S](size_t b) { return (uint64_t)b * S; }, data,
+                     parity, where == MEMO_EC_HOST_PINNED,
+                     [&](const ragged::Range& w, const uint8_t* src, uint8_t* dst, hipStream_t st) {
+                       return encode_device(c, k, m, S, w.b1 - w.b0, src, dst, st);
+                     });
 }
 
 int memo_ec_verify_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const uint8_t* data,
@@ -2172,7 +1963,11 @@ int memo_ec_verify_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const
   DeviceGuard g(c->device);
   if (where == MEMO_EC_DEVICE) return verify_device(c, k, m, S, n, data, parity, verdict, c->stream);
   if (where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
-  return verify_host(c, k, m, S, n, data, parity, verdict, where == MEMO_EC_HOST_PINNED);
+  return verify_host(c, k, m, n, [S](size_t) { return S; }, [S](size_t b) { return (uint64_t)b * S; }, data,
+                     parity, verdict, where == MEMO_EC_HOST_PINNED,
+                     [&](const ragged::Range& w, const uint8_t* d, const uint8_t* p, uint32_t* v, hipStream_t st) {
+                       return verify_device(c, k, m, S, w.b1 - w.b0, d, p, v, st);
+                     });
 }
 
 // The ragged calls' argument checks, all on the host before anything is
@@ -2199,7 +1994,12 @@ int memo_ec_encode_ragged(memo_ec_ctx* c, int k, int m, size_t n, const size_t* 
   DeviceGuard g(c->device);
   if (where == MEMO_EC_DEVICE)
     return ragged_device(c, k, m, n, sizes, off.data(), data, parity, nullptr, c->stream);
-  return encode_ragged_host(c, k, m, n, sizes, off.data(), data, parity, where == MEMO_EC_HOST_PINNED);
+  return encode_host(c, k, m, n, [&](size_t b) { return sizes[b]; }, [&](size_t b) { return off[b]; }, data,
+                     parity, where == MEMO_EC_HOST_PINNED,
+                     [&](const ragged::Range& w, const uint8_t* src, uint8_t* dst, hipStream_t st) {
+                       return ragged_device(c, k, m, w.b1 - w.b0, sizes + w.b0, off.data() + w.b0, src, dst,
+                                            nullptr, st);
+                     });
 }
 
 int memo_ec_verify_ragged(memo_ec_ctx* c, int k, int m, size_t n, const size_t* sizes,
@@ -2218,8 +2018,11 @@ int memo_ec_verify_ragged(memo_ec_ctx* c, int k, int m, size_t n, const size_t* 
   if (where == MEMO_EC_DEVICE)
     return ragged_device(c, k, m, n, sizes, off.data(), data, const_cast<uint8_t*>(parity), verdict,
                          c->stream);
-  return verify_ragged_host(c, k, m, n, sizes, off.data(), data, parity, verdict,
-                            where == MEMO_EC_HOST_PINNED);
+  return verify_host(c, k, m, n, [&](size_t b) { return sizes[b]; }, [&](size_t b) { return off[b]; }, data,
+                     parity, verdict, where == MEMO_EC_HOST_PINNED,
+                     [&](const ragged::Range& w, const uint8_t* d, uint8_t* p, uint32_t* v, hipStream_t st) {
+                       return ragged_device(c, k, m, w.b1 - w.b0, sizes + w.b0, off.data() + w.b0, d, p, v, st);
+                     });
 }
 
 int memo_ec_rebuild_ragged(memo_ec_ctx* c, int k, int m, size_t n, const size_t* sizes,

@@ -1,9 +1,10 @@
 // ragged_plan.h -- GPU-free planning of ragged batches (memo_ec_encode_ragged /
 // memo_ec_verify_ragged / memo_ec_rebuild_ragged): size validation, prefix
 // sums, launch spans, pipeline waves and the per-tile descriptors the ragged
-// kernels read.  Plain C++17, no HIP include: tests/test_ragged_plan.py and
-// tests/test_ragged_rebuild_plan.py build it into stand-alone programs with
-// the host sanitizers.
+// kernels read; at the end (namespace stage) the slot layout of every
+// host-memory call.  Plain C++17, no HIP include: tests/test_ragged_plan.py,
+// tests/test_ragged_rebuild_plan.py and tests/test_stage_plan.py build it
+// into stand-alone programs with the host sanitizers.
 //
 // A ragged batch of n blocks has shard sizes S[b] (multiples of 64, < 2^32,
 // 0 allowed), packed back to back: off[b] = S[0] + ... + S[b-1], T = off[n].
@@ -80,14 +81,16 @@ inline std::vector<Range> cut_spans(const size_t* sizes, size_t n, uint64_t tile
 
 // Pipeline waves: consecutive block ranges that cover every block once, cut
 // on block boundaries only, each of at most byte_limit bytes where block b
-// weighs per * S[b].  A block heavier than the limit gets a wave of its own.
-inline std::vector<Range> cut_waves(const size_t* sizes, size_t n, uint64_t per,
-                                    uint64_t byte_limit) {
+// weighs per * size(b).  A block heavier than the limit gets a wave of its
+// own.  Equal sizes S give max(1, byte_limit / (per * S)) blocks per wave, so
+// the uniform calls cut by the same rule, without a size array.
+template <class Size>
+inline std::vector<Range> cut_waves_by(Size size, size_t n, uint64_t per, uint64_t byte_limit) {
   std::vector<Range> out;
   size_t b0 = 0;
   uint64_t bytes = 0;
   for (size_t b = 0; b < n; ++b) {
-    const uint64_t w = per * (uint64_t)sizes[b];
+    const uint64_t w = per * (uint64_t)size(b);
     if (b > b0 && bytes + w > byte_limit) {
       out.push_back({b0, b});
       b0 = b;
@@ -97,6 +100,10 @@ inline std::vector<Range> cut_waves(const size_t* sizes, size_t n, uint64_t per,
   }
   if (n > b0) out.push_back({b0, n});
   return out;
+}
+inline std::vector<Range> cut_waves(const size_t* sizes, size_t n, uint64_t per,
+                                    uint64_t byte_limit) {
+  return cut_waves_by([sizes](size_t b) { return sizes[b]; }, n, per, byte_limit);
 }
 
 // One tile of the column space.  The index leaves zero-size blocks out:
@@ -313,4 +320,85 @@ inline RowsIndex build_rows_index(const size_t* sizes, size_t n, uint32_t cap) {
 }
 
 }  // namespace ragged
+
+// ---- Staging layout of a host-memory call (memo_ec.cpp: run_staged).  A
+// call is a list of waves, a wave a list of extents of host memory that its
+// kernels read (kIn) or write (kOut).  A kCaller extent is the caller's own
+// buffer (shards, outputs, verdict words): pinned memory is used in place
+// (zero-copy) or moved by DMA directly, pageable memory goes through the
+// ctx's host slot.  A kSlot extent (bytes the library stages: a rebuild's
+// per-block indices) always goes through the host slot.
+// tests/test_stage_plan.py checks the layout on the CPU.
+namespace stage {
+
+enum Dir : uint8_t { kIn, kOut };
+enum Via : uint8_t { kCaller, kSlot };
+constexpr size_t kNone = ~(size_t)0;
+
+struct Extent {
+  void* host;  // kIn extents are only read
+  size_t bytes;
+  Dir dir;
+  Via via;
+  size_t at;   // offset in the wave's device slot
+  size_t hat;  // offset in the wave's host slot; kNone: not staged there (pinned caller memory)
+};
+
+struct Sizes {
+  size_t dev = 0, host = 0;  // the largest wave's device and host slot
+};
+
+struct Plan {
+  std::vector<Extent> ext;
+  std::vector<size_t> first;  // wave w: ext[first[w]] .. ext[first[w + 1]]
+
+  // room for `waves` waves of `extents` extents in all: one allocation each
+  Plan(size_t waves, size_t extents) {
+    ext.reserve(extents);
+    first.reserve(waves + 1);
+    first.push_back(0);
+  }
+  void add(const void* host, size_t bytes, Dir dir, Via via = kCaller) {
+    ext.push_back({const_cast<void*>(host), bytes, dir, via, 0, 0});
+  }
+  // `per` shards of blocks [w.b0, w.b1) of a buffer whose block b starts at
+  // per * off(b)
+  template <class Off>
+  void add_blocks(const ragged::Range& w, Off off, const void* base, uint64_t per, Dir dir) {
+    add(static_cast<const uint8_t*>(base) + per * off(w.b0), (size_t)(per * (off(w.b1) - off(w.b0))), dir);
+  }
+  void end_wave() { first.push_back(ext.size()); }
+  size_t waves() const { return first.size() - 1; }
+
+  // Places every wave's extents in its slot: the caller's inputs in the order
+  // added, then its outputs (each 16-byte aligned: the kernels' vector loads
+  // and stores), then the kSlot bytes, packed.  Inputs and outputs are each
+  // contiguous, so a pageable wave moves with one copy per direction.  A
+  // pageable caller's host slot mirrors the device slot; a pinned caller's
+  // holds the kSlot bytes only -- no pinned bounce buffer of the payload's
+  // size for memory the DMA engines and kernels reach as it lies.
+  Sizes layout(bool pinned) {
+    Sizes sz;
+    for (size_t w = 0; w < waves(); ++w) {
+      size_t at = 0, slot0 = 0;
+      for (int pass = 0; pass < 3; ++pass) {
+        if (pass == 2) slot0 = at;
+        for (size_t i = first[w]; i < first[w + 1]; ++i) {
+          Extent& e = ext[i];
+          if ((e.via == kSlot ? 2 : e.dir == kIn ? 0 : 1) != pass) continue;
+          if (e.via == kCaller) at = (at + 15) & ~(size_t)15;
+          e.at = at;
+          e.hat = e.via == kSlot ? at - (pinned ? slot0 : 0) : pinned ? kNone : at;
+          at += e.bytes;
+        }
+      }
+      sz.dev = sz.dev > at ? sz.dev : at;
+      const size_t h = pinned ? at - slot0 : at;
+      sz.host = sz.host > h ? sz.host : h;
+    }
+    return sz;
+  }
+};
+
+}  // namespace stage
 }  // namespace memo_ec
