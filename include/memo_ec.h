@@ -239,6 +239,47 @@ int memo_ec_verify_batch(memo_ec_ctx *ctx, int k, int m, size_t S, size_t n,
                          const uint8_t *data, const uint8_t *parity,
                          uint32_t *verdict, int where);
 
+/* Do the k + x shards of each block that a caller has in hand agree, and if
+ * not, which one is wrong?  1 <= x <= m; the shards may be any of the k + m,
+ * in any order, so a block with a holder down, or a fetch that came back with
+ * k + 1 shards, can be judged without its missing shards.
+ *
+ * have_idx: n x (k + x) shard indices, one byte each, in the memory `where`
+ *   names, at any byte address.  Per block, entries 0..k-1 are its basis and
+ *   entries k..k+x-1 its spares, in any order.
+ * have: n x (k + x) x S bytes, block-major: block b's shard in position t at
+ *   have + (b * (k + x) + t) * S.  16-byte aligned in MEMO_EC_DEVICE and
+ *   MEMO_EC_HOST_PINNED memory, anywhere in pageable memory.
+ * verdict: n words, 4-byte aligned.  With D (x x k) the decode rows of the
+ *   spares over the basis and s_r = spare r XOR sum_t D[r][t] * basis_t:
+ *   0 = every s_r is zero everywhere.  Otherwise bits 0..15 have bit r set
+ *   iff s_r is nonzero somewhere, and bits 16..23 name the shard INDEX (a
+ *   value of have_idx) that explains every mismatch: have_idx[b][k + r] when
+ *   row r alone differs; have_idx[b][t] when all x rows differ and
+ *   s_r[p] * D[0][t] == D[r][t] * s_0[p] at every byte p and row r (at most
+ *   one t fits); MEMO_EC_VERDICT_UNLOCATED otherwise, and always for x == 1.
+ *   Bits 24..31 are zero.  MEMO_EC_VERDICT_INVALID marks a block whose index
+ *   set holds an index >= k + m or a repeat anywhere among its k + x entries;
+ *   the other blocks are still judged.  With have_idx = 0..k+m-1 and x = m
+ *   the words are those of memo_ec_verify_batch.  As there, a located shard
+ *   is the code's best explanation, not a proof.
+ * A mismatch and an invalid set are results, not errors: the call returns 0,
+ * memo_ec_synchronize reports nothing for them, and an error pending from an
+ * earlier call (MEMO_EC_ESINGULAR of a rebuild) is still reported afterwards.
+ * MEMO_EC_EINVAL: x < 0 or x > m, S no multiple of 64, a NULL or misaligned
+ * pointer, an unknown `where`; MEMO_EC_ERANGE as for the other calls
+ * (n * (k + x) * S); all before anything is enqueued.  x == 0 or n == 0
+ * writes nothing.  S == 0 is allowed: only the index sets are judged, each
+ * word is 0 or MEMO_EC_VERDICT_INVALID, and `have` may be NULL.
+ * MEMO_EC_DEVICE: asynchronous on the ctx stream, every word written by the
+ * call itself; calls back to back need no synchronize between them.  Host
+ * memory goes through the copy pipeline (never zero-copy), in waves cut on
+ * block boundaries. */
+#define MEMO_EC_VERDICT_INVALID 0xFFFFFFFFu
+int memo_ec_check_batch(memo_ec_ctx *ctx, int k, int m, int x, size_t S, size_t n,
+                        const uint8_t *have_idx, const uint8_t *have,
+                        uint32_t *verdict, int where);
+
 /* Ragged batches: n blocks, each with its own shard size, encoded or verified
  * in one call with no padding byte.
  *

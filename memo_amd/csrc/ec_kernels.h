@@ -46,7 +46,10 @@ constexpr int DEC_IDX_REGS = 2;
 // stored parity, read only, and mismatching rows are ORed into `verdict`.
 enum MacMode : int { MAC_ENCODE = 0, MAC_ROWS = 1, MAC_FUSED = 2, MAC_PROBE = 3, MAC_IMAGES = 4,
                      MAC_PERM = 5 /* MEMO_EC_PERM_PROBE builds only (tools/perm_probe.py) */,
-                     MAC_VERIFY = 6 };
+                     MAC_VERIFY = 6,
+                     MAC_CHECK = 7 /* the rows MAC with MAC_VERIFY's compare (gf_check_kernel):
+                                      tables built in LDS from per-block decode rows, `out` the
+                                      block's spares, read only */ };
 
 // LDS bytes of the fused rebuild's decode workspace for a tile of ns blocks:
 // GF log/antilog (1 KiB), LW0 (128 B), per block 3 survivor-mask words + a
@@ -90,7 +93,7 @@ struct MacSeg {
   uint32_t m;             // parity shards of the code (kin + m = shard count)
   uint32_t ws_dw;         // LDS dword offset of the decode workspace
   uint32_t probe;         // stream_probe_kernel: a memo_ec_probe_mode
-  uint32_t* verdict;      // gf_verify_kernel: block b's verdict word at verdict + b
+  uint32_t* verdict;      // gf_verify_kernel, gf_check_kernel: block b's verdict word at verdict + b
 };
 
 struct MacLaunch {
@@ -174,6 +177,19 @@ struct RaggedLocateArgs {
   const uint64_t* boff;  // n + 1 column offsets (off[b] / 16), zero-size blocks included
 };
 
+// memo_ec_check_batch: check_prepare_kernel (have_idx -> verdict, basis,
+// spares) and check_locate_kernel (have_idx, have, rows, verdict).
+struct CheckArgs {
+  const uint8_t* have_idx;  // n x (k + x) shard indices, any byte address
+  const uint8_t* have;      // n x (k + x) x S, block-major (locate only)
+  uint8_t* basis;           // n x k: a block's basis indices (null: not written, S == 0)
+  uint8_t* spares;          // n x x: its spare indices
+  const uint8_t* rows;      // n x x x k decode rows of the spares over the basis (locate only)
+  uint32_t* verdict;        // n words
+  uint64_t n, S;
+  uint32_t k, m, x;
+};
+
 struct FillArgs {
   uint8_t* out;
   uint64_t seed, first_block, n, B, stride;
@@ -211,6 +227,8 @@ hipError_t launch_mac_ragged(int KC, int R, bool verify, const RaggedLaunch& L, 
 hipError_t launch_mac_ragged_rows(int KC, int R, const RaggedLaunch& L, uint32_t grid, size_t lds,
                                   hipStream_t st);
 hipError_t launch_verify_locate_ragged(const RaggedLocateArgs& a, hipStream_t st);
+hipError_t launch_check_prepare(const CheckArgs& a, hipStream_t st);
+hipError_t launch_check_locate(const CheckArgs& a, hipStream_t st);
 hipError_t launch_fill(const FillArgs& a, hipStream_t st);
 hipError_t launch_sha256(const Sha256Args& a, hipStream_t st);
 hipError_t launch_gather(const GatherArgs& a, hipStream_t st);

@@ -1021,8 +1021,11 @@ __device__ __forceinline__ void mac_tile(const MacSeg& sg, uint64_t tile, uint32
                                          const RaggedIdx* rg = nullptr) {
   static_assert(!RAGGED || MODE == MAC_ENCODE || MODE == MAC_VERIFY || MODE == MAC_ROWS,
                 "ragged: encode, verify and the rows rebuild");
-  constexpr bool VERIFY = MODE == MAC_VERIFY;  // the encode path, compare in place of stores
-  constexpr bool COEF = MODE != MAC_ENCODE && !VERIFY;  // tables built in LDS from coefficients
+  static_assert(!RAGGED || MODE != MAC_CHECK, "the check has no ragged form");
+  // compare in place of stores: over the encode path (MAC_VERIFY) or the rows
+  // path (MAC_CHECK: `out` is the block's spares, sg.r = x of them)
+  constexpr bool VERIFY = MODE == MAC_VERIFY || MODE == MAC_CHECK;
+  constexpr bool COEF = MODE != MAC_ENCODE && MODE != MAC_VERIFY;  // tables built in LDS from coefficients
   constexpr bool FUSED = MODE == MAC_FUSED;
   // Verify: the stored parity rows are loaded right behind the shard loads
   // (4 more registers per row live through the MAC: the k = 16, R = 4 body
@@ -1264,6 +1267,23 @@ __global__ void __launch_bounds__(256) gf_verify_kernel(const MacLaunch L) {
   mac_tile<KC, R, NT, MAC_VERIFY>(L.seg[sid], tile, s_tab);
 }
 
+// The check of k + x shards in hand (memo_ec_check_batch): the rows MAC of
+// the two-kernel rebuild -- each tile builds its blocks' tables in LDS from
+// their decode rows (the spares over the basis) -- with the verify's
+// epilogue: the x spares are loaded, not stored, and a lane ORs the rows
+// that differ into its own block's verdict word.  Reads (k + x) * S bytes
+// per block and writes nothing for a consistent one.  A word that
+// check_prepare_kernel set to MEMO_EC_VERDICT_INVALID stays all ones
+// whatever is ORed into it.
+template <int KC, int R, bool NT>
+__global__ void __launch_bounds__(256) gf_check_kernel(const MacLaunch L) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];
+  uint32_t sid;
+  uint64_t tile;
+  if (!seg_tile(L, sid, tile)) return;
+  mac_tile<KC, R, NT, MAC_CHECK>(L.seg[sid], tile, s_tab);
+}
+
 // The shard field (bits 16..23) of the nonzero verdict words: the single
 // shard that explains every mismatch, or 0xFF.  With s_i[p] = stored parity i
 // XOR recomputed parity i at byte p and g_ij = 1 / ((k + i) ^ j):
@@ -1397,6 +1417,139 @@ __global__ void __launch_bounds__(256) verify_locate_kernel(const LocateArgs a) 
 template <int KMAX>
 __global__ void __launch_bounds__(256) verify_locate_ragged_kernel(const RaggedLocateArgs ra) {
   verify_locate_body<KMAX, true>(ra.a, ra.boff);
+}
+
+// ---- memo_ec_check_batch: the kernels around gf_check_kernel.
+
+// One lane per block: is the block's index set valid (every one of its k + x
+// entries below k + m, all distinct: a bit set of k + m <= 80 bits in three
+// registers), its verdict word (0 or MEMO_EC_VERDICT_INVALID: every word of
+// the call is written here, so nothing has to be zeroed first), and the set
+// split into the basis (n x k) and spare (n x x) arrays the decode reads as
+// survivors and lost shards.  An invalid block gets the identity set, 0..k-1
+// and k..k+x-1: the decode and the MAC then run over defined rows and flag
+// nothing, and whatever the MAC ORs into the block's word leaves it all ones.
+// a.basis null (S == 0: only the sets are judged): nothing is split.
+__global__ void __launch_bounds__(256) check_prepare_kernel(const CheckArgs a) {
+  const uint32_t k = a.k, x = a.x, kx = a.k + a.x, nt = a.k + a.m;
+  for (uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x; b < a.n; b += (uint64_t)gridDim.x * 256) {
+    const uint8_t* row = a.have_idx + b * kx;
+    uint32_t w0 = 0, w1 = 0, w2 = 0;
+    bool bad = false;
+    for (uint32_t t = 0; t < kx; ++t) {
+      const uint32_t v = row[t];
+      if (v >= nt) {  // nt <= 80: a valid index has a bit in w0..w2
+        bad = true;
+        continue;
+      }
+      const uint32_t bit = 1u << (v & 31u), wi = v >> 5;
+      const uint32_t seen = wi == 0 ? w0 : wi == 1 ? w1 : w2;
+      bad |= (seen & bit) != 0;
+      w0 |= wi == 0 ? bit : 0u;
+      w1 |= wi == 1 ? bit : 0u;
+      w2 |= wi == 2 ? bit : 0u;
+    }
+    a.verdict[b] = bad ? MEMO_EC_VERDICT_INVALID : 0u;
+    if (!a.basis) continue;
+    uint8_t* bs = a.basis + b * k;
+    uint8_t* sp = a.spares + b * x;
+    for (uint32_t t = 0; t < k; ++t) bs[t] = (uint8_t)(bad ? t : row[t]);
+    for (uint32_t r = 0; r < x; ++r) sp[r] = (uint8_t)(bad ? k + r : row[k + r]);
+  }
+}
+
+// The shard field of the check's nonzero verdict words: verify_locate_kernel's
+// scheme (a fixed grid, 64 words per workgroup round, the flagged blocks taken
+// one at a time by all 256 lanes) with the block's own decode rows D in place
+// of g_ij, its shards taken from `have`, and the answer given as a shard
+// index of have_idx:
+//   the word is MEMO_EC_VERDICT_INVALID -> left as it is
+//   x == 1                              -> 0xFF
+//   one row r lit                       -> have_idx[b][k + r]
+//   all x rows lit, x >= 2              -> have_idx[b][t] for the one basis
+//                                          position t with s_r[p] * D[0][t] ==
+//                                          D[r][t] * s_0[p] at every byte p
+//                                          and row r, else 0xFF
+//   any other mask                      -> 0xFF
+// Every D entry is nonzero (the code is MDS), so a byte with s_0 == 0 and
+// s_r != 0 drops every candidate, as in the verify.
+template <int KMAX>
+__global__ void __launch_bounds__(256) check_locate_kernel(const CheckArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_gf[kGfDwords];
+  __shared__ uint8_t s_d[MEMO_EC_MAX_M * MEMO_EC_MAX_K];  // D[r][t] at r * k + t
+  __shared__ uint32_t s_word[64];
+  __shared__ uint32_t s_cand[2];
+  const uint8_t* lg = reinterpret_cast<const uint8_t*>(s_gf);
+  const uint8_t* ex = lg + 256;
+  const uint32_t k = a.k, x = a.x, kx = a.k + a.x;
+  stage_gf(s_gf);
+  const uint32_t tid = threadIdx.x, lane = tid % 64;
+  const uint32_t all = (1u << x) - 1u;  // x <= 16
+  const uint64_t kbits = k >= 64 ? ~0ull : (1ull << k) - 1ull;
+  const uint64_t dwords = a.S / 4;
+  for (uint64_t base = (uint64_t)blockIdx.x * 64; base < a.n; base += (uint64_t)gridDim.x * 64) {
+    __syncthreads();  // s_gf staged; the previous round's s_word all read
+    if (tid < 64) s_word[tid] = base + tid < a.n ? a.verdict[base + tid] : 0u;
+    __syncthreads();
+    const uint32_t word = s_word[lane];
+    uint64_t flagged = __ballot(word != 0 && word != MEMO_EC_VERDICT_INVALID);
+    while (flagged) {  // uniform over the workgroup: every wave holds the same words
+      const uint32_t src = (uint32_t)__builtin_ctzll(flagged);
+      flagged &= flagged - 1;
+      const uint64_t b = base + src;
+      const uint32_t mask = s_word[src] & 0xFFFFu;
+      const uint8_t* row = a.have_idx + b * kx;
+      uint32_t shard = MEMO_EC_VERDICT_UNLOCATED;
+      if (x >= 2 && __popc(mask) == 1) {
+        shard = row[k + (uint32_t)__builtin_ctz(mask)];
+      } else if (x >= 2 && mask == all) {
+        __syncthreads();  // the previous block's s_d and s_cand all read
+        for (uint32_t i = tid; i < x * k; i += 256) s_d[i] = a.rows[b * (uint64_t)(x * k) + i];
+        if (tid < 2) s_cand[tid] = ~0u;
+        __syncthreads();
+        const uint32_t* d = reinterpret_cast<const uint32_t*>(a.have + b * kx * a.S);
+        const uint32_t* p = d + (uint64_t)k * dwords;  // the block's first spare
+        uint64_t cand = kbits;  // basis positions consistent with every byte this lane saw
+        for (uint64_t w = tid; w < dwords && cand; w += 256) {
+          uint32_t dv[KMAX];
+#pragma unroll
+          for (int j = 0; j < KMAX; ++j) dv[j] = (uint32_t)j < k ? d[j * dwords + w] : 0u;
+          uint32_t pn = p[w], s0 = 0;
+          for (uint32_t i = 0; i < x; ++i) {
+            uint32_t si = pn;  // spare i, then its syndrome
+            if (i + 1 < x) pn = p[(i + 1) * dwords + w];
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j)
+              if ((uint32_t)j < k) si ^= gf_mul4(lg, ex, s_d[i * k + j], dv[j]);
+            if (i == 0) {
+              s0 = si;
+              continue;
+            }
+            if ((s0 | si) == 0) continue;
+            for (uint64_t c = cand; c; c &= c - 1) {
+              const uint32_t j = (uint32_t)__builtin_ctzll(c);
+              if (gf_mul4(lg, ex, s_d[j], si) != gf_mul4(lg, ex, s_d[i * k + j], s0))
+                cand &= ~(1ull << j);
+            }
+          }
+        }
+        // AND over the wave's lanes, then over the workgroup's waves
+        uint32_t lo = (uint32_t)cand, hi = (uint32_t)(cand >> 32);
+        for (int off = 32; off; off >>= 1) {
+          lo &= (uint32_t)__shfl_xor((int)lo, off);
+          hi &= (uint32_t)__shfl_xor((int)hi, off);
+        }
+        if (lane == 0) {
+          atomicAnd(&s_cand[0], lo);
+          atomicAnd(&s_cand[1], hi);
+        }
+        __syncthreads();
+        cand = ((uint64_t)s_cand[1] << 32) | s_cand[0];
+        if (__popcll(cand) == 1) shard = row[(uint32_t)__builtin_ctzll(cand)];
+      }
+      if (tid == 0) a.verdict[b] = mask | (shard << 16);
+    }
+  }
 }
 
 // ---- Ragged encode and verify: mac_tile with the ragged locate, one span
@@ -2322,6 +2475,8 @@ static hipError_t launch_mac_t(int mode, const MacLaunch& L, uint32_t grid, size
     hipLaunchKernelGGL((gf_mac_images_kernel<KC, R, MAC_NT>), dim3(grid), dim3(256), lds, st, L);
   else if (mode == MAC_VERIFY)
     hipLaunchKernelGGL((gf_verify_kernel<KC, R, MAC_NT>), dim3(grid), dim3(256), lds, st, L);
+  else if (mode == MAC_CHECK)
+    hipLaunchKernelGGL((gf_check_kernel<KC, R, MAC_NT>), dim3(grid), dim3(256), lds, st, L);
 #ifdef MEMO_EC_PERM_PROBE
   else if (mode == MAC_PERM)
     hipLaunchKernelGGL((gf_mac_perm_kernel<KC, R, MAC_NT>), dim3(grid), dim3(256), lds, st, L);
@@ -2616,6 +2771,26 @@ hipError_t launch_verify_locate_ragged(const RaggedLocateArgs& ra, hipStream_t s
   else
     hipLaunchKernelGGL(verify_locate_ragged_kernel<MEMO_EC_MAX_K>, dim3((uint32_t)grid), dim3(256), 0,
                        st, ra);
+  return hipGetLastError();
+}
+
+hipError_t launch_check_prepare(const CheckArgs& a, hipStream_t st) {
+  if (a.n == 0) return hipSuccess;
+  // one lane per block; past 2^24 blocks the lanes stride
+  uint64_t grid = (a.n + 255) / 256;
+  if (grid > 65536) grid = 65536;
+  hipLaunchKernelGGL(check_prepare_kernel, dim3((uint32_t)grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_check_locate(const CheckArgs& a, hipStream_t st) {
+  if (a.n == 0) return hipSuccess;
+  uint64_t grid = (a.n + 63) / 64;  // launch_verify_locate's grid
+  if (grid > 2048) grid = 2048;
+  if (a.k <= 16)
+    hipLaunchKernelGGL(check_locate_kernel<16>, dim3((uint32_t)grid), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(check_locate_kernel<MEMO_EC_MAX_K>, dim3((uint32_t)grid), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/memo_ec.h"
+#include "check_plan.h"
 #include "ec_kernels.h"
 #include "ragged_plan.h"
 
@@ -630,8 +631,7 @@ uint64_t launch_tile_limit(const memo_ec_ctx* c) {
 
 // Largest batch (blocks of S-byte shards) one MAC launch takes.
 size_t max_blocks_per_launch(const memo_ec_ctx* c, size_t S) {
-  const uint64_t per = (S / 16 + MAC_TILE - 1) / MAC_TILE + 1;
-  return (size_t)std::max<uint64_t>(1, launch_tile_limit(c) / per);
+  return check::span_blocks(S, launch_tile_limit(c));  // whole tiles + 1 per block (check_plan.h)
 }
 
 // fn(b0, cnt) over n blocks of S-byte shards, in spans one MAC launch takes.
@@ -687,6 +687,55 @@ int verify_device(memo_ec_ctx* ctx, int k, int m, size_t S, size_t n, const uint
   a.k = (uint32_t)k;
   a.m = (uint32_t)m;
   return hip_rc(launch_verify_locate(a, st));
+}
+
+DecodeArgs decode_args(const memo_ec_ctx* c, int k, int m, int e, size_t n, const uint8_t* surv_idx,
+                       const uint8_t* lost_idx, uint8_t* rows, uint32_t* status, const uint32_t* lw0);
+
+// Device-resident check of k + x shards in hand on stream st, over `scratch`
+// (check::scratch_layout(n, k, x).total bytes, 256-byte aligned): the prepare
+// kernel (every verdict word written, have_idx split), the decode rows of
+// the spares over the basis, the check launches (the rows MAC's geometry,
+// split like encode_device's) and the locate pass over the words they
+// flagged.  Every offset comes from check_plan.h.  The decode gets no status
+// word: the prepare kernel hands it valid sets only, and the call leaves the
+// ctx's deferred-error words alone.
+int check_device(memo_ec_ctx* ctx, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                 const uint8_t* have, uint32_t* verdict, uint8_t* scratch, hipStream_t st) {
+  const check::Scratch lay = check::scratch_layout(n, (unsigned)k, (unsigned)x);
+  CheckArgs a{};
+  a.have_idx = have_idx;
+  a.have = have;
+  a.basis = S ? scratch + lay.basis : nullptr;
+  a.spares = S ? scratch + lay.spares : nullptr;
+  a.rows = S ? scratch + lay.rows : nullptr;
+  a.verdict = verdict;
+  a.n = n;
+  a.S = S;
+  a.k = (uint32_t)k;
+  a.m = (uint32_t)m;
+  a.x = (uint32_t)x;
+  HIPCHK(launch_check_prepare(a, st));
+  if (S == 0) return MEMO_EC_OK;
+  uint8_t* rows = scratch + lay.rows;
+  const uint32_t* lw0 = nullptr;
+  if (int rc = lw0_table(ctx, k, m, &lw0)) return rc;
+  HIPCHK(launch_decode_coef(decode_args(ctx, k, m, x, n, a.basis, a.spares, rows, nullptr, lw0), st));
+  const int R = mac_rbound(x), KC = mac_kchunk(k, R);
+  const check::Strides str = check::strides((unsigned)k, (unsigned)x, S);
+  const int rc = launch_spans(ctx, S, n, [&](size_t b0, size_t cnt) {
+    const check::SpanOff o = check::span_offsets(b0, (unsigned)k, (unsigned)x, S);
+    // `out` is the block's spares: MAC_CHECK only reads them
+    Plan p = plan_segment((uint32_t)k, (uint32_t)x, S, cnt, have + o.have, str.block, str.shard,
+                          const_cast<uint8_t*>(have) + o.have + str.spares, str.block, str.shard, nullptr,
+                          0, KC, R, rows + o.rows, str.rows, (uint32_t)x);
+    p.mode = MAC_CHECK;
+    p.seg.verdict = verdict + o.verdict;
+    std::vector<Plan> plans{p};
+    return launch_plans(ctx, plans, st);
+  });
+  if (rc) return rc;
+  return hip_rc(launch_check_locate(a, st));
 }
 
 // ---- Ragged batches (memo_ec_encode_ragged / memo_ec_verify_ragged).
@@ -1176,6 +1225,34 @@ int verify_host(memo_ec_ctx* c, int k, int m, size_t n, Size size, Off off, cons
   }
   return run_staged(c, pl, pinned, false, false, 0, [&](size_t w, const StageView& v, hipStream_t st) {
     return launch(waves[w], v(0), v(1), reinterpret_cast<uint32_t*>(v(2)), st);
+  });
+}
+
+// Host-memory check, as verify_host: each wave's index rows and shards go in,
+// its verdict words come back to their place in the caller's array; always
+// through the copy pipeline.  A wave's kernels use their slot's part of the
+// scratch (check::scratch_layout of the largest wave), which device calls
+// still pending on the ctx stream may be using: the compute stream waits for
+// them first.
+int check_host(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+               const uint8_t* have, uint32_t* verdict, bool pinned) {
+  const size_t kx = (size_t)(k + x);
+  const std::vector<ragged::Range> waves = call_waves(c, false, n, (uint64_t)kx, [S](size_t) { return S; });
+  stage::Plan pl(waves.size(), 3 * waves.size());
+  size_t scratch = 0;
+  for (const ragged::Range& w : waves) {
+    const check::SpanOff o = check::span_offsets(w.b0, (unsigned)k, (unsigned)x, S);
+    const size_t cnt = w.b1 - w.b0;
+    pl.add(S ? have + o.have : nullptr, cnt * kx * S, stage::kIn);
+    pl.add(have_idx + w.b0 * kx, cnt * kx, stage::kIn);
+    pl.add(verdict + o.verdict, cnt * sizeof(uint32_t), stage::kOut);
+    pl.end_wave();
+    scratch = std::max(scratch, check::scratch_layout(cnt, (unsigned)k, (unsigned)x).total);
+  }
+  if (int rc = wait_device_rebuilds(c)) return rc;
+  return run_staged(c, pl, pinned, false, false, scratch, [&](size_t w, const StageView& v, hipStream_t st) {
+    return check_device(c, k, m, x, S, waves[w].b1 - waves[w].b0, v(1), v(0),
+                        reinterpret_cast<uint32_t*>(v(2)), v.scratch, st);
   });
 }
 
@@ -1968,6 +2045,27 @@ int memo_ec_verify_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const
                      [&](const ragged::Range& w, const uint8_t* d, const uint8_t* p, uint32_t* v, hipStream_t st) {
                        return verify_device(c, k, m, S, w.b1 - w.b0, d, p, v, st);
                      });
+}
+
+int memo_ec_check_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                        const uint8_t* have, uint32_t* verdict, int where) {
+  if (!c) return MEMO_EC_EINVAL;
+  if (int rc = check_km(k, m)) return rc;
+  if (x < 0 || x > m) return MEMO_EC_EINVAL;
+  if (where != MEMO_EC_DEVICE && where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
+  if (x == 0 || n == 0) return MEMO_EC_OK;
+  if (S % 64 != 0 || !have_idx || !verdict || (S && !have)) return MEMO_EC_EINVAL;
+  if ((S && shard_misaligned(where, have)) || misaligned(verdict, 4)) return MEMO_EC_EINVAL;
+  // the index rows count too: with S == 0 they are all the call moves
+  if (S >= kMaxShard || too_big(n, (size_t)(k + x) * std::max<size_t>(S, 1))) return MEMO_EC_ERANGE;
+  DeviceGuard g(c->device);
+  if (where != MEMO_EC_DEVICE) return check_host(c, k, m, x, S, n, have_idx, have, verdict, where == MEMO_EC_HOST_PINNED);
+  if (int rc = ensure_tabs(c, S ? check::scratch_layout(n, (unsigned)k, (unsigned)x).total : 0)) return rc;
+  if (int rc = check_device(c, k, m, x, S, n, have_idx, have, verdict, reinterpret_cast<uint8_t*>(c->d_tabs),
+                            c->stream))
+    return rc;
+  // marks the scratch busy until the check is done (host calls check it)
+  return S ? hip_rc(hipEventRecord(c->ev_order, c->stream)) : MEMO_EC_OK;
 }
 
 // The ragged calls' argument checks, all on the host before anything is

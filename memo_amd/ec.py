@@ -64,6 +64,7 @@ _ROOT = os.path.dirname(_HERE)
 BUILD_SOURCES = [os.path.join(_ROOT, "include", "memo_ec.h"),
                  os.path.join(_HERE, "csrc", "ec_kernels.h"),
                  os.path.join(_HERE, "csrc", "ragged_plan.h"),
+                 os.path.join(_HERE, "csrc", "check_plan.h"),
                  os.path.join(_HERE, "csrc", "ec_kernels.hip"),
                  os.path.join(_HERE, "csrc", "memo_ec.cpp")]
 
@@ -81,10 +82,13 @@ EXPORTS = [
     "memo_ec_ctx_set_option", "memo_ec_ctx_get_option", "memo_ec_build_id",
     "memo_ec_device_identity", "memo_ec_stream_probe", "memo_ec_verify_batch",
     "memo_ec_encode_ragged", "memo_ec_verify_ragged", "memo_ec_rebuild_ragged",
+    "memo_ec_check_batch",
 ]
 
 # memo_ec_verify_batch verdict words: MEMO_EC_VERDICT_UNLOCATED of the header.
 VERDICT_UNLOCATED = 0xFF
+# memo_ec_check_batch: the word of a block whose index set is invalid.
+VERDICT_INVALID = 0xFFFFFFFF
 
 
 def split_verdict(v):
@@ -155,6 +159,9 @@ def _lib():
         if hasattr(L, "memo_ec_rebuild_ragged"):
             L.memo_ec_rebuild_ragged.argtypes = [ctypes.c_void_p, c_int, c_int, _sz, ctypes.c_void_p,
                                                  _u8p, _u8p, _u8p, c_int, c_int, _u8p, c_int]
+        if hasattr(L, "memo_ec_check_batch"):
+            L.memo_ec_check_batch.argtypes = [ctypes.c_void_p, c_int, c_int, c_int, _sz, _sz, _u8p, _u8p,
+                                              ctypes.c_void_p, c_int]
         _LIB = L
     return _LIB
 
@@ -417,6 +424,59 @@ class Codec:
             raise ValueError("verdict must live where the shards do (device or host)")
         where = DEVICE if dw == DEVICE else (HOST_PINNED if dw == pw == vw == HOST_PINNED else HOST)
         _check(_lib().memo_ec_verify_batch(self._ctx, k, m, S, n, dp, pp, vp, where), "verify")
+        return verdict
+
+    def check(self, k, m, have_idx, have, verdict=None, x=None, S=None, n=None):
+        """memo_ec_check_batch: verdict (n words) <- do the k + x shards in
+        hand of each block agree: 0, mask | shard << 16 (split_verdict; shard
+        is a shard INDEX, a value of have_idx) or VERDICT_INVALID for an
+        invalid index set.  have_idx: n x (k + x) uint8 (basis, then spares);
+        have: n x (k + x) x S bytes in that order; both numpy arrays or torch
+        tensors in one kind of memory.  x comes from a 2-D have_idx, n and S
+        from have_idx and what have holds, unless given.  verdict: a numpy
+        uint32 array or torch int32 tensor of n words in the memory the shards
+        live in (made when None); device (async) or host (sync)."""
+        if x is None:
+            if len(have_idx.shape) != 2:
+                raise ValueError("x is needed unless have_idx is n x (k + x)")
+            x = int(have_idx.shape[1]) - k
+        if not 0 <= x <= m:
+            raise ValueError("x = %d, need 0 <= x <= m = %d" % (x, m))
+        idx_len = have_idx.numel() if _is_torch(have_idx) else have_idx.size
+        if n is None:
+            if idx_len % (k + x):
+                raise ValueError("have_idx does not hold rows of k + x = %d indices" % (k + x))
+            n = idx_len // (k + x)
+        elif idx_len < n * (k + x):
+            raise ValueError("have_idx holds %d indices, need %d" % (idx_len, n * (k + x)))
+        have_len = 0 if have is None else have.numel() if _is_torch(have) else have.size  # None: S == 0
+        if S is None:
+            if n == 0 or have_len % (n * (k + x)):
+                raise ValueError("have does not hold n x (k + x) shards of one size; pass S")
+            S = have_len // (n * (k + x))
+        elif have_len < n * (k + x) * S:
+            raise ValueError("have holds %d bytes, need %d" % (have_len, n * (k + x) * S))
+        ip, iw = _ptr(have_idx)
+        hp, hw = (0, iw) if have is None else _ptr(have)
+        if (iw == DEVICE) != (hw == DEVICE):
+            raise ValueError("have_idx and have must both be device or both host buffers")
+        if verdict is None:
+            # Every word is written by the call itself, on the ctx stream
+            # (see verify()); x == 0 or n == 0: nothing is written.
+            written = x > 0 and n > 0
+            if _is_torch(have_idx):
+                import torch
+                make = torch.empty if written else torch.zeros
+                verdict = make(n, dtype=torch.int32, device=have_idx.device,
+                               pin_memory=(iw == hw == HOST_PINNED))
+            else:
+                verdict = (np.empty if written else np.zeros)(n, dtype=np.uint32)
+        vp, vw = _ptr_words(verdict, n)
+        if (vw == DEVICE) != (hw == DEVICE):
+            raise ValueError("verdict must live where the shards do (device or host)")
+        where = DEVICE if hw == DEVICE else (HOST_PINNED if iw == hw == vw == HOST_PINNED else HOST)
+        _check(_lib().memo_ec_check_batch(self._ctx, k, m, x, S, n, ip or None, hp or None, vp or None,
+                                          where), "check")
         return verdict
 
     def encode_ragged(self, k, m, sizes, data, parity):
