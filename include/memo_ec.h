@@ -280,6 +280,50 @@ int memo_ec_check_batch(memo_ec_ctx *ctx, int k, int m, int x, size_t S, size_t 
                         const uint8_t *have_idx, const uint8_t *have,
                         uint32_t *verdict, int where);
 
+/* memo_ec_check_batch, and the wrong shard of every located block mended in
+ * place, on the device, with no host round trip between the two.
+ *
+ * The call first does exactly what memo_ec_check_batch does, with the same
+ * arguments: the same layout of have_idx, have and verdict, the same
+ * alignment rules, MEMO_EC_EINVAL / MEMO_EC_ERANGE cases, empty-call rules
+ * (x == 0 or n == 0 writes nothing) and meaning of `where`.  `have` is
+ * written here, so it is not const.
+ *
+ * A block is located when its word is nonzero, is not
+ * MEMO_EC_VERDICT_INVALID, its shard field is not MEMO_EC_VERDICT_UNLOCATED,
+ * and S > 0.  For every located block, the shard in the position q with
+ * have_idx[b][q] == MEMO_EC_VERDICT_SHARD(word) is overwritten in `have`.
+ * With D (x x k) the block's decode rows of the spares over the basis, the
+ * new bytes are, by definition,
+ *   q >= k (spare r = q - k):  sum_t D[r][t] * basis_t
+ *   q <  k (a basis shard):    inv(D[0][q]) * (spare_0 XOR
+ *                                sum_{t != q} D[0][t] * basis_t)
+ * -- a one-row multiply-accumulate over k shards that never reads the wrong
+ * one.  Bit 24 of the block's word (MEMO_EC_VERDICT_CORRECTED) is then set;
+ * bits 0..23 stay the check's word, bits 25..31 are zero.  No other byte of
+ * `have` is written: clean, unlocated and invalid blocks are untouched.
+ *
+ * So a block with one wrong shard gets that shard's true bytes back, and a
+ * memo_ec_check_batch of the same buffers afterwards gives 0 for every
+ * corrected block.  With x == 1, or S == 0, the call is memo_ec_check_batch.
+ * With have_idx = 0..k+m-1 and x = m it corrects what memo_ec_verify_batch
+ * locates.  A located shard is the code's best explanation, not a proof:
+ * with x = 2 two wrong shards can pass for one, the call then overwrites a
+ * shard that may have been right, and the old bytes are not kept.  Callers
+ * check the mended block against its hash.
+ *
+ * A correction is a result, not an error: the return value and
+ * memo_ec_synchronize behave as for the check.  MEMO_EC_DEVICE: asynchronous
+ * on the ctx stream, no host synchronisation inside the call; calls back to
+ * back need no synchronize between them.  Host memory goes through the copy
+ * pipeline (never zero-copy), in the check's waves, cut on block boundaries;
+ * a wave moves the check's bytes plus S bytes back per corrected block,
+ * never the whole wave. */
+#define MEMO_EC_VERDICT_CORRECTED(v) ((((uint32_t)(v)) >> 24) & 1u)  /* only for v != MEMO_EC_VERDICT_INVALID */
+int memo_ec_correct_batch(memo_ec_ctx *ctx, int k, int m, int x, size_t S, size_t n,
+                          const uint8_t *have_idx, uint8_t *have,
+                          uint32_t *verdict, int where);
+
 /* Ragged batches: n blocks, each with its own shard size, encoded or verified
  * in one call with no padding byte.
  *

@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "correct_plan.h"
 #include "ec_kernels.h"
 
 namespace memo_ec {
@@ -1552,6 +1553,119 @@ __global__ void __launch_bounds__(256) check_locate_kernel(const CheckArgs a) {
   }
 }
 
+// ---- memo_ec_correct_batch: the two kernels behind the check's.
+
+// The work list of the located blocks: a fixed grid strides over the verdict
+// words, one word per lane.  A word is located when it is neither 0 nor
+// MEMO_EC_VERDICT_INVALID and names a shard; its position q is where have_idx
+// holds that shard.  Each wave ballots its located words, adds their number
+// to the count word with one atomic and writes its entries behind what it got
+// back, so the list is dense and in no particular order; each lane sets bit
+// 24 of its own word.  Every lane of a workgroup runs the same rounds (the
+// ballot wants whole waves).
+__global__ void __launch_bounds__(256) correct_list_kernel(const CorrectArgs a) {
+  const uint32_t kx = a.k + a.x, lane = threadIdx.x % 64;
+  unsigned long long* count = reinterpret_cast<unsigned long long*>(a.count);
+  for (uint64_t base = (uint64_t)blockIdx.x * 256; base < a.n; base += (uint64_t)gridDim.x * 256) {
+    const uint64_t b = base + threadIdx.x;
+    const uint32_t word = b < a.n ? a.verdict[b] : 0u;
+    const uint32_t shard = MEMO_EC_VERDICT_SHARD(word);
+    uint32_t q = kx;
+    if (word != 0 && word != MEMO_EC_VERDICT_INVALID && shard != MEMO_EC_VERDICT_UNLOCATED) {
+      const uint8_t* row = a.have_idx + b * kx;
+      for (uint32_t t = 0; t < kx; ++t) q = row[t] == shard ? t : q;
+    }
+    const bool located = q < kx;
+    const uint64_t votes = __ballot(located);
+    if (votes == 0) continue;  // uniform over the wave
+    unsigned long long first = 0;
+    if (lane == 0) first = atomicAdd(count, (unsigned long long)__popcll(votes));
+    const uint32_t flo = (uint32_t)__shfl((int)(uint32_t)first, 0);
+    const uint32_t fhi = (uint32_t)__shfl((int)(uint32_t)(first >> 32), 0);
+    if (located) {
+      const uint64_t rank = (uint64_t)__popcll(votes & ((1ull << lane) - 1ull));
+      a.list[(((uint64_t)fhi << 32) | flo) + rank] = correct::make_entry(b, q);
+      a.verdict[b] = word | (1u << 24);
+    }
+  }
+}
+
+// The correction: the located shards' new bytes, one 4 KiB tile of one list
+// entry per work item, the items dealt to a fixed grid in contiguous ranges
+// (correct_plan.h).  The count is read from device memory (uniform; the list
+// kernel's atomics are visible across the kernel boundary); a clean batch
+// finds 0 and leaves.  Per entry the lanes t < k form the k coefficients from
+// the block's decode rows -- row q - k as it is for a spare target, row 0
+// scaled by 1 / D[0][q] for a basis target, with 1 / D[0][q] itself in slot q,
+// where spare 0 stands in for the basis shard -- and build their product
+// tables in LDS (the rows path's split layout, one set, R = 1).  A workgroup
+// keeps the images across the consecutive tiles of one entry.  Per tile each
+// lane loads its 16-byte column of the k inputs, runs the MAC's chunk body and
+// stores 16 bytes of the target; lanes past S / 16 neither load nor store.
+// The target is never read, and no other byte of `have` is written.
+template <int KC>
+__global__ void __launch_bounds__(256) gf_correct_kernel(const CorrectArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_gf[kGfDwords];
+  __shared__ __attribute__((aligned(16))) uint32_t s_tab[5 * MEMO_EC_MAX_K];  // q: 4 dwords a slot; lo: 1
+  const uint64_t tpb = correct::tiles_per_block(a.S);
+  const uint64_t total = correct::work_items(*reinterpret_cast<const unsigned long long*>(a.count), tpb);
+  const correct::ItemRange mine = correct::wg_items(total, gridDim.x, blockIdx.x);
+  if (mine.first >= mine.end) return;
+  const uint8_t* lg = reinterpret_cast<const uint8_t*>(s_gf);
+  const uint8_t* ex = lg + 256;
+  const uint32_t k = a.k, kpad = (k + KC - 1) / KC * KC, t = threadIdx.x;
+  MacSeg sg{};
+  sg.lo_dw = 4 * MEMO_EC_MAX_K;
+  TabRef<true> tab;
+  tab.q = s_tab;
+  tab.l = s_tab + sg.lo_dw;
+  stage_gf(s_gf);
+  uint64_t cur = ~0ull;
+  for (uint64_t w = mine.first; w < mine.end; ++w) {
+    const correct::Item it = correct::item_of(w, tpb);
+    const uint64_t e = a.list[it.entry];
+    const uint64_t b = correct::entry_block(e);
+    const uint32_t q = correct::entry_pos(e);
+    if (it.entry != cur) {  // uniform over the workgroup
+      __syncthreads();  // s_gf staged; the previous entry's images all read
+      if (t < kpad) {
+        uint32_t c = 0;
+        if (t < k) {
+          const uint8_t* row = a.rows + correct::row_off(b, q, k, a.x);
+          c = row[t];
+          if (q < k) {
+            const uint32_t inv = ex[255u - lg[row[q]]];
+            c = t == q ? inv : gf_mul_t(lg, ex, inv, c);
+          }
+        }
+        uint4 qv;
+        uint32_t lo;
+        coef_image(c, qv, lo);
+        put_image(s_tab, sg, kpad, t, qv, lo);
+      }
+      __syncthreads();
+      cur = it.entry;
+    }
+    const uint64_t col = correct::col_off(it.tile, t);
+    const bool active = col < a.S;
+    uint32_t acc[1][4] = {{0u, 0u, 0u, 0u}};
+    for (uint32_t j0 = 0; j0 < k; j0 += KC) {
+      uint4 d[KC];
+#pragma unroll
+      for (int g = 0; g < KC; ++g) {
+        d[g] = make_uint4(0u, 0u, 0u, 0u);
+        if (active && j0 + g < k)
+          d[g] = ld16<MAC_NT>(a.have + correct::shard_off(b, correct::input_pos(j0 + g, q, k), k, a.x, a.S) +
+                              col);
+      }
+      mac_chunk<KC, 1, true>(acc, d, tab, kpad, j0);
+    }
+    if (active)
+      st16<MAC_NT>(a.have + correct::shard_off(b, q, k, a.x, a.S) + col,
+                   make_uint4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]));
+  }
+}
+
 // ---- Ragged encode and verify: mac_tile with the ragged locate, one span
 // per launch, under names of their own (as gf_mac_images_kernel) so the
 // uniform kernels' code is not disturbed.
@@ -2792,6 +2906,34 @@ hipError_t launch_check_locate(const CheckArgs& a, hipStream_t st) {
   else
     hipLaunchKernelGGL(check_locate_kernel<MEMO_EC_MAX_K>, dim3((uint32_t)grid), dim3(256), 0, st, a);
   return hipGetLastError();
+}
+
+hipError_t launch_correct_list(const CorrectArgs& a, hipStream_t st) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(correct_list_kernel, dim3(correct::list_grid_for(a.n)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// gf_correct_kernel over the shard chunks the MAC is compiled for, R = 1.
+template <int KC>
+static hipError_t launch_correct_kc(const CorrectArgs& a, uint32_t grid, hipStream_t st) {
+  hipLaunchKernelGGL(gf_correct_kernel<KC>, dim3(grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_correct(const CorrectArgs& a, hipStream_t st) {
+  const uint32_t grid = correct::grid_for(a.n, a.S);
+  if (grid == 0) return hipSuccess;
+  switch (mac_kchunk((int)a.k, 1)) {
+    case 2: return launch_correct_kc<2>(a, grid, st);
+    case 3: return launch_correct_kc<3>(a, grid, st);
+    case 4: return launch_correct_kc<4>(a, grid, st);
+    case 6: return launch_correct_kc<6>(a, grid, st);
+    case 10: return launch_correct_kc<10>(a, grid, st);
+    case 12: return launch_correct_kc<12>(a, grid, st);
+    case 14: return launch_correct_kc<14>(a, grid, st);
+    case 16: return launch_correct_kc<16>(a, grid, st);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 hipError_t launch_fill(const FillArgs& a, hipStream_t st) {

@@ -20,6 +20,7 @@
 
 #include "../../include/memo_ec.h"
 #include "check_plan.h"
+#include "correct_plan.h"
 #include "ec_kernels.h"
 #include "ragged_plan.h"
 
@@ -738,6 +739,33 @@ int check_device(memo_ec_ctx* ctx, int k, int m, int x, size_t S, size_t n, cons
   return hip_rc(launch_check_locate(a, st));
 }
 
+// Device-resident check-and-mend on stream st, over `scratch`
+// (correct::scratch_layout(n, k, x).total bytes, 256-byte aligned, the
+// check's scratch at its start): check_device, then the count word zeroed,
+// the list of the located blocks and the correction over it, all in stream
+// order with no host synchronisation.  x == 1 or S == 0 locates nothing: the
+// call is the check.
+int correct_device(memo_ec_ctx* ctx, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                   uint8_t* have, uint32_t* verdict, uint8_t* scratch, hipStream_t st) {
+  if (int rc = check_device(ctx, k, m, x, S, n, have_idx, have, verdict, scratch, st)) return rc;
+  if (S == 0 || x < 2) return MEMO_EC_OK;
+  const correct::Scratch lay = correct::scratch_layout(n, (unsigned)k, (unsigned)x);
+  CorrectArgs a{};
+  a.have_idx = have_idx;
+  a.have = have;
+  a.rows = scratch + lay.chk.rows;
+  a.verdict = verdict;
+  a.count = reinterpret_cast<uint64_t*>(scratch + lay.count);
+  a.list = reinterpret_cast<uint64_t*>(scratch + lay.list);
+  a.n = n;
+  a.S = S;
+  a.k = (uint32_t)k;
+  a.x = (uint32_t)x;
+  HIPCHK(hipMemsetAsync(a.count, 0, sizeof(uint64_t), st));
+  HIPCHK(launch_correct_list(a, st));
+  return hip_rc(launch_correct(a, st));
+}
+
 // ---- Ragged batches (memo_ec_encode_ragged / memo_ec_verify_ragged).
 
 constexpr size_t kIdxPoolMax = 8;
@@ -1087,7 +1115,10 @@ struct StageView {
 // Runs a host-memory call.  `pl`: its waves (zc: one); `scratch`: bytes of
 // d_tabs a wave's kernels use; `status`: the call reports what its kernels
 // flag in StageView::status (a rebuild's singular blocks); run(w, view, st)
-// enqueues wave w's kernels on st.
+// enqueues wave w's kernels on st.  `hook` (optional; nothing by default):
+// hook(w, device slot, copy-out stream) runs on the host once wave w's
+// outputs have arrived in the caller's memory and before its device slot is
+// reused (the copy pipeline only).
 //  - zc: the kernels read the wave from, and write their output to, pinned
 //    host memory over PCIe -- no DMA copies to wait for.  A pinned caller's
 //    buffers are used where they lie, a pageable caller's are copied through
@@ -1095,9 +1126,12 @@ struct StageView {
 //  - else the 3-stage pipeline of run_waves: bounce copies of pageable
 //    memory and kSlot bytes, HtoD, kernels, DtoH, bounce copies back.  A
 //    pinned caller's buffers are the DMA's source and target.
-template <class Run>
+struct NoWaveHook {
+  int operator()(size_t, uint8_t*, hipStream_t) const { return MEMO_EC_OK; }
+};
+template <class Run, class Hook = NoWaveHook>
 int run_staged(memo_ec_ctx* c, stage::Plan& pl, bool pinned, bool zc, bool status, size_t scratch,
-               Run run) {
+               Run run, Hook hook = Hook()) {
   const stage::Sizes sz = pl.layout(pinned);
   // wave w's `dir` extents between the caller's memory and host slot h
   auto bounce = [&](size_t w, uint8_t* h, stage::Dir dir) {
@@ -1159,7 +1193,9 @@ int run_staged(memo_ec_ctx* c, stage::Plan& pl, bool pinned, bool zc, bool statu
     return flush();
   };
   const size_t nw = pl.waves();
-  const int rc = run_waves(
+  const hipStream_t s_hook = nw == 1 ? c->sk : c->sd;  // run_waves' copy-out stream
+  int hook_rc = MEMO_EC_OK;
+  int rc = run_waves(
       c, nw,
       [&](int s, size_t w, hipStream_t st) -> int {
         bounce(w, c->h_slot[s], stage::kIn);
@@ -1180,7 +1216,11 @@ int run_staged(memo_ec_ctx* c, stage::Plan& pl, bool pinned, bool zc, bool statu
                                 hipMemcpyDeviceToHost, st));
         return MEMO_EC_OK;
       },
-      [&](int s, size_t w) { bounce(w, c->h_slot[s], stage::kOut); });
+      [&](int s, size_t w) {
+        bounce(w, c->h_slot[s], stage::kOut);
+        if (hook_rc == MEMO_EC_OK) hook_rc = hook(w, c->d_slot[s], s_hook);
+      });
+  if (rc == MEMO_EC_OK) rc = hook_rc;
   if (rc || !status) return rc;
   const uint32_t st = *c->h_status;
   if (st) {
@@ -1254,6 +1294,55 @@ int check_host(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const ui
     return check_device(c, k, m, x, S, waves[w].b1 - waves[w].b0, v(1), v(0),
                         reinterpret_cast<uint32_t*>(v(2)), v.scratch, st);
   });
+}
+
+// Host-memory check-and-mend: check_host's waves and copies, the wave's
+// kernels being correct_device's.  Once a wave's verdict words have arrived,
+// each corrected block's mended shard (S bytes) is copied from the wave's
+// device slot to its place in the caller's `have`, before the slot is reused:
+// a wave moves the check's bytes plus S per corrected block, never all of it.
+int correct_host(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                 uint8_t* have, uint32_t* verdict, bool pinned) {
+  const size_t kx = (size_t)(k + x);
+  const std::vector<ragged::Range> waves = call_waves(c, false, n, (uint64_t)kx, [S](size_t) { return S; });
+  stage::Plan pl(waves.size(), 3 * waves.size());
+  size_t scratch = 0;
+  for (const ragged::Range& w : waves) {
+    const check::SpanOff o = check::span_offsets(w.b0, (unsigned)k, (unsigned)x, S);
+    const size_t cnt = w.b1 - w.b0;
+    pl.add(S ? have + o.have : nullptr, cnt * kx * S, stage::kIn);
+    pl.add(have_idx + w.b0 * kx, cnt * kx, stage::kIn);
+    pl.add(verdict + o.verdict, cnt * sizeof(uint32_t), stage::kOut);
+    pl.end_wave();
+    scratch = std::max(scratch, correct::scratch_layout(cnt, (unsigned)k, (unsigned)x).total);
+  }
+  if (int rc = wait_device_rebuilds(c)) return rc;
+  return run_staged(
+      c, pl, pinned, false, false, scratch,
+      [&](size_t w, const StageView& v, hipStream_t st) {
+        return correct_device(c, k, m, x, S, waves[w].b1 - waves[w].b0, v(1), v(0),
+                              reinterpret_cast<uint32_t*>(v(2)), v.scratch, st);
+      },
+      [&](size_t w, uint8_t* dslot, hipStream_t st) -> int {
+        if (S == 0 || x < 2) return MEMO_EC_OK;
+        const uint8_t* dhave = dslot + pl.ext[pl.first[w]].at;  // the wave's `have` in its slot
+        bool any = false;
+        for (size_t b = waves[w].b0; b < waves[w].b1; ++b) {
+          const uint32_t word = verdict[b];
+          if (word == MEMO_EC_VERDICT_INVALID || !MEMO_EC_VERDICT_CORRECTED(word)) continue;
+          const uint8_t* row = have_idx + b * kx;
+          for (uint32_t q = 0; q < kx; ++q) {
+            if (row[q] != MEMO_EC_VERDICT_SHARD(word)) continue;
+            HIPCHK(hipMemcpyAsync(have + correct::shard_off(b, q, (uint32_t)k, (uint32_t)x, S),
+                                  dhave + correct::shard_off(b - waves[w].b0, q, (uint32_t)k, (uint32_t)x, S),
+                                  S, hipMemcpyDeviceToHost, st));
+            any = true;
+            break;
+          }
+        }
+        if (any) HIPCHK(hipStreamSynchronize(st));
+        return MEMO_EC_OK;
+      });
 }
 
 // Decode rows of one erasure pattern on the host: row r = C[lost_r] *
@@ -2065,6 +2154,28 @@ int memo_ec_check_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n,
                             c->stream))
     return rc;
   // marks the scratch busy until the check is done (host calls check it)
+  return S ? hip_rc(hipEventRecord(c->ev_order, c->stream)) : MEMO_EC_OK;
+}
+
+int memo_ec_correct_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                          uint8_t* have, uint32_t* verdict, int where) {
+  // the argument checks of memo_ec_check_batch, in its order
+  if (!c) return MEMO_EC_EINVAL;
+  if (int rc = check_km(k, m)) return rc;
+  if (x < 0 || x > m) return MEMO_EC_EINVAL;
+  if (where != MEMO_EC_DEVICE && where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
+  if (x == 0 || n == 0) return MEMO_EC_OK;
+  if (S % 64 != 0 || !have_idx || !verdict || (S && !have)) return MEMO_EC_EINVAL;
+  if ((S && shard_misaligned(where, have)) || misaligned(verdict, 4)) return MEMO_EC_EINVAL;
+  if (S >= kMaxShard || too_big(n, (size_t)(k + x) * std::max<size_t>(S, 1))) return MEMO_EC_ERANGE;
+  DeviceGuard g(c->device);
+  if (where != MEMO_EC_DEVICE)
+    return correct_host(c, k, m, x, S, n, have_idx, have, verdict, where == MEMO_EC_HOST_PINNED);
+  if (int rc = ensure_tabs(c, S ? correct::scratch_layout(n, (unsigned)k, (unsigned)x).total : 0)) return rc;
+  if (int rc = correct_device(c, k, m, x, S, n, have_idx, have, verdict, reinterpret_cast<uint8_t*>(c->d_tabs),
+                              c->stream))
+    return rc;
+  // marks the scratch busy until the call is done (host calls check it)
   return S ? hip_rc(hipEventRecord(c->ev_order, c->stream)) : MEMO_EC_OK;
 }
 

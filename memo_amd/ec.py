@@ -65,6 +65,7 @@ BUILD_SOURCES = [os.path.join(_ROOT, "include", "memo_ec.h"),
                  os.path.join(_HERE, "csrc", "ec_kernels.h"),
                  os.path.join(_HERE, "csrc", "ragged_plan.h"),
                  os.path.join(_HERE, "csrc", "check_plan.h"),
+                 os.path.join(_HERE, "csrc", "correct_plan.h"),
                  os.path.join(_HERE, "csrc", "ec_kernels.hip"),
                  os.path.join(_HERE, "csrc", "memo_ec.cpp")]
 
@@ -82,13 +83,26 @@ EXPORTS = [
     "memo_ec_ctx_set_option", "memo_ec_ctx_get_option", "memo_ec_build_id",
     "memo_ec_device_identity", "memo_ec_stream_probe", "memo_ec_verify_batch",
     "memo_ec_encode_ragged", "memo_ec_verify_ragged", "memo_ec_rebuild_ragged",
-    "memo_ec_check_batch",
+    "memo_ec_check_batch", "memo_ec_correct_batch",
 ]
 
 # memo_ec_verify_batch verdict words: MEMO_EC_VERDICT_UNLOCATED of the header.
 VERDICT_UNLOCATED = 0xFF
 # memo_ec_check_batch: the word of a block whose index set is invalid.
 VERDICT_INVALID = 0xFFFFFFFF
+
+
+def verdict_corrected(v):
+    """MEMO_EC_VERDICT_CORRECTED of memo_ec_correct_batch's word(s) v: bit 24,
+    the located shard was rewritten; False for VERDICT_INVALID.  Takes an int
+    (-> bool), a numpy array or a torch tensor (-> a numpy bool array)."""
+    if _is_torch(v):
+        v = v.detach().cpu().numpy()
+    if isinstance(v, np.ndarray):
+        u = v.astype(np.int64) & 0xFFFFFFFF
+        return (u != VERDICT_INVALID) & (((u >> 24) & 1) == 1)
+    u = int(v) & 0xFFFFFFFF
+    return u != VERDICT_INVALID and bool((u >> 24) & 1)
 
 
 def split_verdict(v):
@@ -162,6 +176,9 @@ def _lib():
         if hasattr(L, "memo_ec_check_batch"):
             L.memo_ec_check_batch.argtypes = [ctypes.c_void_p, c_int, c_int, c_int, _sz, _sz, _u8p, _u8p,
                                               ctypes.c_void_p, c_int]
+        if hasattr(L, "memo_ec_correct_batch"):
+            L.memo_ec_correct_batch.argtypes = [ctypes.c_void_p, c_int, c_int, c_int, _sz, _sz, _u8p, _u8p,
+                                                ctypes.c_void_p, c_int]
         _LIB = L
     return _LIB
 
@@ -436,6 +453,26 @@ class Codec:
         from have_idx and what have holds, unless given.  verdict: a numpy
         uint32 array or torch int32 tensor of n words in the memory the shards
         live in (made when None); device (async) or host (sync)."""
+        x, S, n, ip, hp, vp, where, verdict = self._check_args(k, m, have_idx, have, verdict, x, S, n)
+        _check(_lib().memo_ec_check_batch(self._ctx, k, m, x, S, n, ip or None, hp or None, vp or None,
+                                          where), "check")
+        return verdict
+
+    def correct(self, k, m, have_idx, have, verdict=None, x=None, S=None, n=None):
+        """memo_ec_correct_batch: check(), and the wrong shard of every
+        located block rewritten in `have` on the device; such a block's word
+        is the check's with bit 24 set (verdict_corrected).  Arguments as for
+        check(); `have` is written.  A located shard is the code's best
+        explanation, not a proof: check the mended block against its hash."""
+        x, S, n, ip, hp, vp, where, verdict = self._check_args(k, m, have_idx, have, verdict, x, S, n)
+        _check(_lib().memo_ec_correct_batch(self._ctx, k, m, x, S, n, ip or None, hp or None, vp or None,
+                                            where), "correct")
+        return verdict
+
+    @staticmethod
+    def _check_args(k, m, have_idx, have, verdict, x, S, n):
+        """The argument checks of check() and correct():
+        (x, S, n, have_idx pointer, have pointer, verdict pointer, where, verdict)."""
         if x is None:
             if len(have_idx.shape) != 2:
                 raise ValueError("x is needed unless have_idx is n x (k + x)")
@@ -475,9 +512,7 @@ class Codec:
         if (vw == DEVICE) != (hw == DEVICE):
             raise ValueError("verdict must live where the shards do (device or host)")
         where = DEVICE if hw == DEVICE else (HOST_PINNED if iw == hw == vw == HOST_PINNED else HOST)
-        _check(_lib().memo_ec_check_batch(self._ctx, k, m, x, S, n, ip or None, hp or None, vp or None,
-                                          where), "check")
-        return verdict
+        return x, S, n, ip, hp, vp, where, verdict
 
     def encode_ragged(self, k, m, sizes, data, parity):
         """memo_ec_encode_ragged: blocks of their own shard sizes (sizes[b],
