@@ -324,6 +324,62 @@ int memo_ec_correct_batch(memo_ec_ctx *ctx, int k, int m, int x, size_t S, size_
                           const uint8_t *have_idx, uint8_t *have,
                           uint32_t *verdict, int where);
 
+/* memo_ec_check_batch, and for every block it leaves unlocated the TWO wrong
+ * shards, when exactly one pair of shards explains every mismatch.
+ *
+ * The call is memo_ec_check_batch followed by one more kernel over the same
+ * buffers: the same arguments, layout of have_idx, have and verdict,
+ * alignment rules, MEMO_EC_EINVAL / MEMO_EC_ERANGE cases in the same order
+ * before anything is enqueued, empty-call rules (x == 0 or n == 0 writes
+ * nothing) and meaning of `where`.  Nothing but verdict words is written.
+ *
+ * With D (x x k) and the syndromes s_r of the check, let s[p] be the vector
+ * (s_0[p], ..., s_{x-1}[p]) at byte p and H = [D | I_x] the x x (k + x)
+ * matrix with one column per POSITION q of have_idx: column q < k is D[:, q],
+ * column k + r the unit vector e_r.  A set E of positions explains the block
+ * when s[p] lies in span{H_q : q in E} at every byte p.  (The check's shard
+ * field is "some one position explains".)  The word is memo_ec_check_batch's,
+ * bit for bit, unless x >= 3, S > 0, that word is nonzero, is not
+ * MEMO_EC_VERDICT_INVALID, its shard field is MEMO_EC_VERDICT_UNLOCATED, and
+ * EXACTLY ONE pair of positions {a, b} explains the block.  Then
+ *   bits 0..15   stay the check's mask;
+ *   bits 16..23  hold the smaller of the two shard INDICES have_idx[b][a],
+ *                have_idx[b][b];
+ *   bit 24       is zero;
+ *   bits 25..31  hold the larger index plus 1 (1..80, as k + m <= 80):
+ *                MEMO_EC_VERDICT_HAS_PAIR / MEMO_EC_VERDICT_SHARD2.
+ * In every word that names no pair bits 25..31 are zero;
+ * MEMO_EC_VERDICT_INVALID stays all ones.
+ *
+ * The code is MDS, so any min(x, .) columns of H are independent.  x >= 4:
+ * at most one pair can explain an unlocated block, so two wrong shards are
+ * always named, whatever their bytes.  x == 3: the pair is unique when the
+ * syndrome vectors span two dimensions; when they are all proportional (one
+ * wrong byte at the same offset of both shards, say) two pairs can explain
+ * the block, and the word then stays unlocated.  x <= 2, or S == 0: the call
+ * is memo_ec_check_batch.
+ *
+ * A located pair is the code's best explanation, not a proof: three wrong
+ * shards can pass for two (as two can pass for one in the check with x = 2).
+ * Callers rebuild the two shards from the others and check the block against
+ * its hash.  MEMO_EC_VERDICT_SHARD of a pair word gives the smaller index and
+ * so reads like a one-shard answer: callers of THIS call test
+ * MEMO_EC_VERDICT_HAS_PAIR first.  No other call produces such words, and
+ * memo_ec_correct_batch never sees one.
+ *
+ * Results are not errors: the return value and memo_ec_synchronize behave as
+ * for the check, and the ctx's deferred errors are left alone.
+ * MEMO_EC_DEVICE: asynchronous on the ctx stream; calls back to back need no
+ * synchronize between them.  Host memory goes through the copy pipeline in
+ * the check's waves: the same bytes in, the same words out.  The extra
+ * kernel reads the n verdict words, and the shards of the unlocated blocks
+ * up to three times more. */
+#define MEMO_EC_VERDICT_HAS_PAIR(v) ((uint32_t)(v) != MEMO_EC_VERDICT_INVALID && (((uint32_t)(v)) >> 25) != 0u)
+#define MEMO_EC_VERDICT_SHARD2(v) (((((uint32_t)(v)) >> 25) & 0x7Fu) - 1u)  /* the larger index; only if HAS_PAIR */
+int memo_ec_check_pair_batch(memo_ec_ctx *ctx, int k, int m, int x, size_t S, size_t n,
+                             const uint8_t *have_idx, const uint8_t *have,
+                             uint32_t *verdict, int where);
+
 /* Ragged batches: n blocks, each with its own shard size, encoded or verified
  * in one call with no padding byte.
  *

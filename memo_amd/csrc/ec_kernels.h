@@ -178,7 +178,9 @@ struct RaggedLocateArgs {
 };
 
 // memo_ec_check_batch: check_prepare_kernel (have_idx -> verdict, basis,
-// spares) and check_locate_kernel (have_idx, have, rows, verdict).
+// spares) and check_locate_kernel (have_idx, have, rows, verdict);
+// memo_ec_check_pair_batch: check_pair_kernel after them (what the locate
+// kernel reads; it writes verdict words only).
 struct CheckArgs {
   const uint8_t* have_idx;  // n x (k + x) shard indices, any byte address
   const uint8_t* have;      // n x (k + x) x S, block-major (locate only)
@@ -244,6 +246,8 @@ hipError_t launch_mac_ragged_rows(int KC, int R, const RaggedLaunch& L, uint32_t
 hipError_t launch_verify_locate_ragged(const RaggedLocateArgs& a, hipStream_t st);
 hipError_t launch_check_prepare(const CheckArgs& a, hipStream_t st);
 hipError_t launch_check_locate(const CheckArgs& a, hipStream_t st);
+// check_pair_kernel over the words the locate pass left (x >= 3, S > 0)
+hipError_t launch_check_pair(const CheckArgs& a, hipStream_t st);
 hipError_t launch_correct_list(const CorrectArgs& a, hipStream_t st);
 // gf_correct_kernel<KC>, KC = mac_kchunk(k, 1)
 hipError_t launch_correct(const CorrectArgs& a, hipStream_t st);

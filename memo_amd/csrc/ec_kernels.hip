@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "check_pair_logic.h"
 #include "correct_plan.h"
 #include "ec_kernels.h"
 
@@ -1553,6 +1554,184 @@ __global__ void __launch_bounds__(256) check_locate_kernel(const CheckArgs a) {
   }
 }
 
+// ---- memo_ec_check_pair_batch: one kernel behind the check's.
+
+// The two wrong shards of the blocks check_locate_kernel left unlocated, on
+// its scheme: a fixed grid, 64 verdict words per workgroup round, the
+// qualifying blocks (word nonzero, not MEMO_EC_VERDICT_INVALID, shard field
+// 0xFF) taken one at a time by all 256 lanes, D staged in LDS, the syndrome
+// dwords formed with gf_mul4.  With H = [D | I_x] (one column per position of
+// have_idx) a pair of positions explains the block when every syndrome
+// vector s[p] lies in span{H_a, H_b}; the word is rewritten when exactly one
+// pair does (check_pair_logic.h holds the algebra and the word's layout):
+//   1  any nonzero syndrome vector is v1: the lanes walk the block's dwords,
+//      the lowest byte offset wins (atomicMin in LDS), x lanes form v1 there;
+//   2  a second walk takes as v2 any syndrome that is no multiple of v1;
+//   3a there is one (rank >= 2): a third walk tests every syndrome against
+//      span{v1, v2}; one outside it (rank >= 3) leaves the word as it is.
+//      Otherwise the lanes q < k + x test H_q against the span: it is a pair
+//      when exactly two columns pass (any three columns are independent for
+//      x >= 3, so this is "exactly one pair explains");
+//   3b there is none (rank 1): the lanes stride over the C(k + x, 2) <= 3160
+//      pairs and count those with rank [H_a H_b v1] == 2; it is a pair when
+//      the count is one.
+// Every condition around a __syncthreads is read from LDS after a barrier,
+// so it is uniform over the workgroup.  The kernel reads have_idx, have, the
+// decode rows and the verdict words, and writes verdict words only.  The
+// syndromes of an unlocated block are computed up to three times: the cold
+// path, as the locate pass is.
+struct PairShared {
+  pair_logic::Span span;
+  uint8_t vec[MEMO_EC_MAX_M];  // v1, then v2, as x lanes formed it
+  uint32_t at;                 // lowest byte offset a walk found, or ~0u
+  uint32_t fail;               // walk 3a: a syndrome outside the span
+  uint32_t count, lo, hi;      // passing columns / explaining pairs
+};
+
+// Row i of the syndrome dword of a lane's position: spare i XOR the decode
+// row over the basis dwords dv.
+template <int KMAX>
+__device__ __forceinline__ uint32_t pair_syn_row(const uint8_t* lg, const uint8_t* ex, const uint8_t* s_d,
+                                                 uint32_t k, uint32_t i, const uint32_t (&dv)[KMAX],
+                                                 uint32_t spare) {
+  uint32_t si = spare;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j)
+    if ((uint32_t)j < k) si ^= gf_mul4(lg, ex, s_d[i * k + j], dv[j]);
+  return si;
+}
+
+// One walk over the block's dwords.  WALK 1: any nonzero syndrome; 2: any
+// outside span (dimension 1); 3: any outside span (dimension 2).  The first
+// hit of a lane ends its walk: its byte offset goes into sh.at (walks 1, 2)
+// or sh.fail is set (walk 3).
+template <int KMAX, int WALK>
+__device__ __forceinline__ void pair_walk(const uint8_t* lg, const uint8_t* ex, const uint8_t* s_d,
+                                          PairShared& sh, const uint32_t* d, uint32_t k, uint32_t x,
+                                          uint64_t dwords) {
+  const uint32_t* p = d + (uint64_t)k * dwords;  // the block's first spare
+  const auto mul4 = [lg, ex](uint32_t c, uint32_t v) { return gf_mul4(lg, ex, c, v); };
+  const uint32_t p0 = sh.span.p0, p1 = sh.span.p1;
+  for (uint64_t w = threadIdx.x; w < dwords; w += 256) {
+    uint32_t dv[KMAX];
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) dv[j] = (uint32_t)j < k ? d[j * dwords + w] : 0u;
+    uint32_t s0 = 0, s1 = 0, bad = 0;
+    if (WALK >= 2) s0 = pair_syn_row<KMAX>(lg, ex, s_d, k, p0, dv, p[p0 * dwords + w]);
+    if (WALK == 3) s1 = pair_syn_row<KMAX>(lg, ex, s_d, k, p1, dv, p[p1 * dwords + w]);
+    uint32_t pn = p[w];
+    for (uint32_t i = 0; i < x; ++i) {
+      const uint32_t spare = pn;
+      if (i + 1 < x) pn = p[(i + 1) * dwords + w];
+      const uint32_t si = pair_syn_row<KMAX>(lg, ex, s_d, k, i, dv, spare);
+      if constexpr (WALK == 1)
+        bad |= si;
+      else
+        bad |= pair_logic::span_residual(sh.span, i, si, s0, s1, mul4);
+    }
+    if (bad == 0) continue;
+    if (WALK == 3)
+      sh.fail = 1u;
+    else  // S < 2^32: a byte offset fits a word
+      atomicMin(&sh.at, (uint32_t)(w * 4) + ((uint32_t)__builtin_ctz(bad) >> 3));
+    break;
+  }
+}
+
+template <int KMAX>
+__global__ void __launch_bounds__(256) check_pair_kernel(const CheckArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_gf[kGfDwords];
+  __shared__ uint8_t s_d[MEMO_EC_MAX_M * MEMO_EC_MAX_K];  // D[r][t] at r * k + t
+  __shared__ uint32_t s_word[64];
+  __shared__ PairShared sh;
+  const uint8_t* lg = reinterpret_cast<const uint8_t*>(s_gf);
+  const uint8_t* ex = lg + 256;
+  const auto mul1 = [lg, ex](uint32_t c, uint32_t v) { return gf_mul_t(lg, ex, c, v); };
+  const uint32_t k = a.k, x = a.x, kx = a.k + a.x;
+  stage_gf(s_gf);
+  const uint32_t tid = threadIdx.x, lane = tid % 64;
+  const uint64_t dwords = a.S / 4;
+  for (uint64_t base = (uint64_t)blockIdx.x * 64; base < a.n; base += (uint64_t)gridDim.x * 64) {
+    __syncthreads();  // s_gf staged; the previous round's s_word all read
+    if (tid < 64) s_word[tid] = base + tid < a.n ? a.verdict[base + tid] : 0u;
+    __syncthreads();
+    const uint32_t word = s_word[lane];
+    uint64_t todo = __ballot(word != 0 && word != MEMO_EC_VERDICT_INVALID &&
+                             MEMO_EC_VERDICT_SHARD(word) == MEMO_EC_VERDICT_UNLOCATED);
+    while (todo) {  // uniform over the workgroup: every wave holds the same words
+      const uint32_t src = (uint32_t)__builtin_ctzll(todo);
+      todo &= todo - 1;
+      const uint64_t b = base + src;
+      const uint8_t* row = a.have_idx + b * kx;
+      const uint8_t* hv = a.have + b * kx * a.S;
+      const uint32_t* d = reinterpret_cast<const uint32_t*>(hv);
+      // x lanes: the syndrome vector at byte `at` into sh.vec
+      const auto form = [&](uint32_t at) {
+        if (tid < x) {
+          uint32_t s = hv[(uint64_t)(k + tid) * a.S + at];
+          for (uint32_t t = 0; t < k; ++t) s ^= mul1(s_d[tid * k + t], hv[(uint64_t)t * a.S + at]);
+          sh.vec[tid] = (uint8_t)s;
+        }
+      };
+      __syncthreads();  // the previous block's s_d and sh all read
+      for (uint32_t i = tid; i < x * k; i += 256) s_d[i] = a.rows[b * (uint64_t)(x * k) + i];
+      if (tid == 0) {
+        sh.at = ~0u;
+        sh.fail = 0u;
+        sh.count = 0u;
+        sh.lo = ~0u;
+        sh.hi = 0u;
+        sh.span.p0 = sh.span.p1 = 0u;
+      }
+      __syncthreads();
+      pair_walk<KMAX, 1>(lg, ex, s_d, sh, d, k, x, dwords);
+      __syncthreads();
+      const uint32_t at1 = sh.at;
+      if (at1 == ~0u) continue;  // no syndrome at all: not what the check saw; leave the word
+      form(at1);
+      __syncthreads();  // sh.vec written, sh.at read
+      if (tid == 0) {
+        pair_logic::span_set1(sh.span, x, sh.vec);
+        sh.at = ~0u;
+      }
+      __syncthreads();
+      pair_walk<KMAX, 2>(lg, ex, s_d, sh, d, k, x, dwords);
+      __syncthreads();
+      const uint32_t at2 = sh.at;
+      uint32_t want = 1u;  // rank 1: one pair; rank 2: two columns
+      if (at2 != ~0u) {    // rank >= 2
+        form(at2);
+        __syncthreads();
+        if (tid == 0) pair_logic::span_set2(sh.span, sh.vec, mul1);
+        __syncthreads();
+        pair_walk<KMAX, 3>(lg, ex, s_d, sh, d, k, x, dwords);
+        __syncthreads();
+        if (sh.fail || sh.span.dim != 2) continue;  // rank >= 3
+        if (tid < kx && pair_logic::column_in_span(sh.span, s_d, k, tid, mul1)) {
+          atomicAdd(&sh.count, 1u);  // at most two columns pass: any three are independent
+          atomicMin(&sh.lo, tid);
+          atomicMax(&sh.hi, tid);
+        }
+        want = 2u;
+      } else {  // rank 1: every syndrome is a multiple of v1 = sh.span.u1
+        const uint32_t pairs = kx * (kx - 1) / 2;
+        for (uint32_t t = tid; t < pairs; t += 256) {
+          uint32_t qa, qb;
+          pair_logic::nth_pair(kx, t, qa, qb);
+          if (pair_logic::pair_explains(s_d, k, x, sh.span.u1, qa, qb, mul1)) {
+            atomicAdd(&sh.count, 1u);
+            sh.lo = qa;  // read only when the count is one: a single writer
+            sh.hi = qb;
+          }
+        }
+      }
+      __syncthreads();
+      if (tid == 0 && sh.count == want && sh.lo < sh.hi && sh.hi < kx)
+        a.verdict[b] = pair_logic::pair_word(s_word[src], row[sh.lo], row[sh.hi]);
+    }
+  }
+}
+
 // ---- memo_ec_correct_batch: the two kernels behind the check's.
 
 // The work list of the located blocks: a fixed grid strides over the verdict
@@ -2905,6 +3084,17 @@ hipError_t launch_check_locate(const CheckArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(check_locate_kernel<16>, dim3((uint32_t)grid), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(check_locate_kernel<MEMO_EC_MAX_K>, dim3((uint32_t)grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_check_pair(const CheckArgs& a, hipStream_t st) {
+  if (a.n == 0) return hipSuccess;
+  uint64_t grid = (a.n + 63) / 64;  // launch_check_locate's grid
+  if (grid > 2048) grid = 2048;
+  if (a.k <= 16)
+    hipLaunchKernelGGL(check_pair_kernel<16>, dim3((uint32_t)grid), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(check_pair_kernel<MEMO_EC_MAX_K>, dim3((uint32_t)grid), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

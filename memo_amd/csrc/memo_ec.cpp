@@ -700,9 +700,12 @@ DecodeArgs decode_args(const memo_ec_ctx* c, int k, int m, int e, size_t n, cons
 // split like encode_device's) and the locate pass over the words they
 // flagged.  Every offset comes from check_plan.h.  The decode gets no status
 // word: the prepare kernel hands it valid sets only, and the call leaves the
-// ctx's deferred-error words alone.
+// ctx's deferred-error words alone.  `pair` (memo_ec_check_pair_batch): one
+// more launch over the same arguments, check_pair_kernel, for the words the
+// locate pass left unlocated; it needs x >= 3 and S > 0 to find anything.
 int check_device(memo_ec_ctx* ctx, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
-                 const uint8_t* have, uint32_t* verdict, uint8_t* scratch, hipStream_t st) {
+                 const uint8_t* have, uint32_t* verdict, uint8_t* scratch, hipStream_t st,
+                 bool pair = false) {
   const check::Scratch lay = check::scratch_layout(n, (unsigned)k, (unsigned)x);
   CheckArgs a{};
   a.have_idx = have_idx;
@@ -736,7 +739,9 @@ int check_device(memo_ec_ctx* ctx, int k, int m, int x, size_t S, size_t n, cons
     return launch_plans(ctx, plans, st);
   });
   if (rc) return rc;
-  return hip_rc(launch_check_locate(a, st));
+  HIPCHK(launch_check_locate(a, st));
+  if (pair && x >= 3) HIPCHK(launch_check_pair(a, st));
+  return MEMO_EC_OK;
 }
 
 // Device-resident check-and-mend on stream st, over `scratch`
@@ -1273,9 +1278,10 @@ int verify_host(memo_ec_ctx* c, int k, int m, size_t n, Size size, Off off, cons
 // through the copy pipeline.  A wave's kernels use their slot's part of the
 // scratch (check::scratch_layout of the largest wave), which device calls
 // still pending on the ctx stream may be using: the compute stream waits for
-// them first.
+// them first.  `pair`: the wave's kernels are memo_ec_check_pair_batch's; the
+// same bytes move in and the same words move out.
 int check_host(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
-               const uint8_t* have, uint32_t* verdict, bool pinned) {
+               const uint8_t* have, uint32_t* verdict, bool pinned, bool pair) {
   const size_t kx = (size_t)(k + x);
   const std::vector<ragged::Range> waves = call_waves(c, false, n, (uint64_t)kx, [S](size_t) { return S; });
   stage::Plan pl(waves.size(), 3 * waves.size());
@@ -1292,7 +1298,7 @@ int check_host(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const ui
   if (int rc = wait_device_rebuilds(c)) return rc;
   return run_staged(c, pl, pinned, false, false, scratch, [&](size_t w, const StageView& v, hipStream_t st) {
     return check_device(c, k, m, x, S, waves[w].b1 - waves[w].b0, v(1), v(0),
-                        reinterpret_cast<uint32_t*>(v(2)), v.scratch, st);
+                        reinterpret_cast<uint32_t*>(v(2)), v.scratch, st, pair);
   });
 }
 
@@ -2136,8 +2142,9 @@ int memo_ec_verify_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const
                      });
 }
 
-int memo_ec_check_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
-                        const uint8_t* have, uint32_t* verdict, int where) {
+// memo_ec_check_batch and memo_ec_check_pair_batch (`pair`): one contract.
+static int check_call(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                      const uint8_t* have, uint32_t* verdict, int where, bool pair) {
   if (!c) return MEMO_EC_EINVAL;
   if (int rc = check_km(k, m)) return rc;
   if (x < 0 || x > m) return MEMO_EC_EINVAL;
@@ -2148,13 +2155,24 @@ int memo_ec_check_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n,
   // the index rows count too: with S == 0 they are all the call moves
   if (S >= kMaxShard || too_big(n, (size_t)(k + x) * std::max<size_t>(S, 1))) return MEMO_EC_ERANGE;
   DeviceGuard g(c->device);
-  if (where != MEMO_EC_DEVICE) return check_host(c, k, m, x, S, n, have_idx, have, verdict, where == MEMO_EC_HOST_PINNED);
+  if (where != MEMO_EC_DEVICE)
+    return check_host(c, k, m, x, S, n, have_idx, have, verdict, where == MEMO_EC_HOST_PINNED, pair);
   if (int rc = ensure_tabs(c, S ? check::scratch_layout(n, (unsigned)k, (unsigned)x).total : 0)) return rc;
   if (int rc = check_device(c, k, m, x, S, n, have_idx, have, verdict, reinterpret_cast<uint8_t*>(c->d_tabs),
-                            c->stream))
+                            c->stream, pair))
     return rc;
   // marks the scratch busy until the check is done (host calls check it)
   return S ? hip_rc(hipEventRecord(c->ev_order, c->stream)) : MEMO_EC_OK;
+}
+
+int memo_ec_check_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                        const uint8_t* have, uint32_t* verdict, int where) {
+  return check_call(c, k, m, x, S, n, have_idx, have, verdict, where, false);
+}
+
+int memo_ec_check_pair_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n,
+                             const uint8_t* have_idx, const uint8_t* have, uint32_t* verdict, int where) {
+  return check_call(c, k, m, x, S, n, have_idx, have, verdict, where, true);
 }
 
 int memo_ec_correct_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,

@@ -66,6 +66,7 @@ BUILD_SOURCES = [os.path.join(_ROOT, "include", "memo_ec.h"),
                  os.path.join(_HERE, "csrc", "ragged_plan.h"),
                  os.path.join(_HERE, "csrc", "check_plan.h"),
                  os.path.join(_HERE, "csrc", "correct_plan.h"),
+                 os.path.join(_HERE, "csrc", "check_pair_logic.h"),
                  os.path.join(_HERE, "csrc", "ec_kernels.hip"),
                  os.path.join(_HERE, "csrc", "memo_ec.cpp")]
 
@@ -83,7 +84,7 @@ EXPORTS = [
     "memo_ec_ctx_set_option", "memo_ec_ctx_get_option", "memo_ec_build_id",
     "memo_ec_device_identity", "memo_ec_stream_probe", "memo_ec_verify_batch",
     "memo_ec_encode_ragged", "memo_ec_verify_ragged", "memo_ec_rebuild_ragged",
-    "memo_ec_check_batch", "memo_ec_correct_batch",
+    "memo_ec_check_batch", "memo_ec_correct_batch", "memo_ec_check_pair_batch",
 ]
 
 # memo_ec_verify_batch verdict words: MEMO_EC_VERDICT_UNLOCATED of the header.
@@ -118,6 +119,23 @@ def split_verdict(v):
         return (u & 0xFFFF).astype(np.uint32), ((u >> 16) & 0xFF).astype(np.uint32)
     u = int(v) & 0xFFFFFFFF
     return u & 0xFFFF, (u >> 16) & 0xFF
+
+
+def split_verdict_pair(v):
+    """(mask, shard, second) of memo_ec_check_pair_batch's word(s) v: second
+    is the larger shard index of a located pair (MEMO_EC_VERDICT_SHARD2; shard
+    is then the smaller), None when the word names no pair.  An int gives
+    ints; a numpy array or a torch tensor gives numpy arrays, second being -1
+    where there is no pair.  Not for VERDICT_INVALID."""
+    if _is_torch(v):
+        v = v.detach().cpu().numpy()
+    if isinstance(v, np.ndarray):
+        u = v.astype(np.int64) & 0xFFFFFFFF
+        return ((u & 0xFFFF).astype(np.uint32), ((u >> 16) & 0xFF).astype(np.uint32),
+                (((u >> 25) & 0x7F) - 1).astype(np.int32))
+    u = int(v) & 0xFFFFFFFF
+    hi = (u >> 25) & 0x7F
+    return u & 0xFFFF, (u >> 16) & 0xFF, hi - 1 if hi else None
 
 
 def _lib():
@@ -179,6 +197,9 @@ def _lib():
         if hasattr(L, "memo_ec_correct_batch"):
             L.memo_ec_correct_batch.argtypes = [ctypes.c_void_p, c_int, c_int, c_int, _sz, _sz, _u8p, _u8p,
                                                 ctypes.c_void_p, c_int]
+        if hasattr(L, "memo_ec_check_pair_batch"):
+            L.memo_ec_check_pair_batch.argtypes = [ctypes.c_void_p, c_int, c_int, c_int, _sz, _sz, _u8p,
+                                                   _u8p, ctypes.c_void_p, c_int]
         _LIB = L
     return _LIB
 
@@ -469,9 +490,21 @@ class Codec:
                                             where), "correct")
         return verdict
 
+    def check_pair(self, k, m, have_idx, have, verdict=None, x=None, S=None, n=None):
+        """memo_ec_check_pair_batch: check(), and for the blocks it leaves
+        unlocated (x >= 3) the two wrong shards, when exactly one pair of
+        shards explains every mismatch: mask | smaller index << 16 | (larger
+        index + 1) << 25 (split_verdict_pair).  Arguments as for check().  A
+        located pair is the code's best explanation, not a proof: check the
+        rebuilt block against its hash."""
+        x, S, n, ip, hp, vp, where, verdict = self._check_args(k, m, have_idx, have, verdict, x, S, n)
+        _check(_lib().memo_ec_check_pair_batch(self._ctx, k, m, x, S, n, ip or None, hp or None,
+                                               vp or None, where), "check_pair")
+        return verdict
+
     @staticmethod
     def _check_args(k, m, have_idx, have, verdict, x, S, n):
-        """The argument checks of check() and correct():
+        """The argument checks of check(), correct() and check_pair():
         (x, S, n, have_idx pointer, have pointer, verdict pointer, where, verdict)."""
         if x is None:
             if len(have_idx.shape) != 2:
