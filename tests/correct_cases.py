@@ -25,10 +25,13 @@ EDGES = [(5, 3, 3, 4160, 6), (5, 3, 3, 64, 6), (10, 4, 2, 4160, 6), (10, 4, 2, 6
 LIST = (3, 2, 2, 64, 4099)
 SPLIT = (10, 4, 4, 4160, 5)
 MISLOCATED = [(3, 2, 2, 64), (10, 4, 2, 64)]   # (k, m, x, S)
+# tests/test_gpu_check_sweep.py: 3 tiles an entry (the last 64 bytes), 2100 work
+# items over 2048 workgroups, so item ranges begin and end inside entries
+SWEEP_RANGES = (3, 2, 2, 8256, 700)
 
 # (k, m, x, S, n) of every device test, for the CPU walk of correct_plan.h
 NOTHING = [(10, 4, 3, 448, 24), (16, 4, 2, 8256, 3)]   # invalid sets; a clean batch of several tiles a block
-GPU_SHAPES = (list(SHAPES) + [BRINGUP, WAVES, LIST, SPLIT] + EDGES + NOTHING
+GPU_SHAPES = (list(SHAPES) + [BRINGUP, WAVES, LIST, SPLIT, SWEEP_RANGES] + EDGES + NOTHING
               + [(k, KC_M, x, KC_S, KC_N) for KC in KCS for k in KC_CODES[KC] for x in (2, KC_M)]
               + [(k, m, x, S, k) for (k, m, x, S) in MISLOCATED]   # k such blocks each (see there)
               + [(k, m, m, 128, 16) for (k, m) in [(3, 2), (10, 4), (7, 5)]])
