@@ -361,11 +361,12 @@ int memo_ec_correct_batch(memo_ec_ctx *ctx, int k, int m, int x, size_t S, size_
  *
  * A located pair is the code's best explanation, not a proof: three wrong
  * shards can pass for two (as two can pass for one in the check with x = 2).
- * Callers rebuild the two shards from the others and check the block against
- * its hash.  MEMO_EC_VERDICT_SHARD of a pair word gives the smaller index and
- * so reads like a one-shard answer: callers of THIS call test
- * MEMO_EC_VERDICT_HAS_PAIR first.  No other call produces such words, and
- * memo_ec_correct_batch never sees one.
+ * Callers rebuild the two shards from the others (memo_ec_correct_pair_batch
+ * does it on the device) and check the block against its hash.
+ * MEMO_EC_VERDICT_SHARD of a pair word gives the smaller index and so reads
+ * like a one-shard answer: callers of THIS call test MEMO_EC_VERDICT_HAS_PAIR
+ * first.  Only this call and memo_ec_correct_pair_batch produce such words,
+ * and memo_ec_correct_batch never sees one.
  *
  * Results are not errors: the return value and memo_ec_synchronize behave as
  * for the check, and the ctx's deferred errors are left alone.
@@ -379,6 +380,62 @@ int memo_ec_correct_batch(memo_ec_ctx *ctx, int k, int m, int x, size_t S, size_
 int memo_ec_check_pair_batch(memo_ec_ctx *ctx, int k, int m, int x, size_t S, size_t n,
                              const uint8_t *have_idx, const uint8_t *have,
                              uint32_t *verdict, int where);
+
+/* memo_ec_check_pair_batch, and every block with one or two wrong shards
+ * mended in place, on the device, with no host round trip in between.
+ *
+ * The arguments, the layout of have_idx, have and verdict, the alignment
+ * rules, the MEMO_EC_EINVAL / MEMO_EC_ERANGE cases (same order, before
+ * anything is enqueued), the empty-call rules (x == 0 or n == 0 writes
+ * nothing) and the meaning of `where` are exactly memo_ec_correct_batch's.
+ *
+ * Single-located blocks (the check names one shard): the call does what
+ * memo_ec_correct_batch does: the same bytes written, the same word (bits
+ * 0..23 the check's, bit 24 set, bits 25..31 zero).
+ *
+ * Pair blocks (memo_ec_check_pair_batch would return a pair word: x >= 3,
+ * S > 0, exactly one pair of positions qa < qb explains the block): both named
+ * shards are overwritten in `have`, and the word is the pair word with bit 24
+ * (MEMO_EC_VERDICT_CORRECTED) set.  MEMO_EC_VERDICT_HAS_PAIR, _SHARD, _SHARD2
+ * and _CORRECTED all read correctly from it.
+ *
+ * Every other block -- clean, invalid, unlocated with no unique pair --: the
+ * word is memo_ec_check_pair_batch's, and not a byte of `have` is written.
+ *
+ * The new bytes of a pair block are, by definition, the rebuild of the two
+ * named shards, as memo_ec_rebuild_batch with e = 2 gives it, from the k
+ * INPUT POSITIONS of the block taken in this fixed order: basis position j
+ * (j < k) is input slot j; the slot of each basis target is filled by a spare
+ * position that is not a target, the lowest such spare positions being used
+ * in ascending order.  So
+ *   two spare targets                  read the k basis shards;
+ *   basis target q, spare target k + r read the basis without q, and spare c
+ *                                      in slot q: c = 0 if r != 0, else 1;
+ *   basis targets q1 < q2              read the basis without them, spare 0 in
+ *                                      slot q1 and spare 1 in slot q2.
+ * The two targets and the remaining spares are never read.  The code is MDS:
+ * any k positions determine the block, so the rebuild is unique; the fixed
+ * choice matters only when more than two shards are wrong.
+ *
+ * So a memo_ec_check_batch of the same buffers afterwards gives 0 for every
+ * corrected block, single or pair: a unique explaining pair means that the
+ * other k + x - 2 positions lie on one codeword.  As ever this is the code's
+ * best explanation, not a proof: three wrong shards can pass for two, the call
+ * then overwrites two shards that may have been right, and the old bytes are
+ * not kept.  Callers check the mended block against its hash.
+ *
+ * x <= 2: the call is memo_ec_correct_batch.  S == 0, x == 0 or n == 0: as
+ * there.  A correction is a result, not an error: the return value and
+ * memo_ec_synchronize behave as for the check, and the ctx's deferred errors
+ * are left alone.  MEMO_EC_DEVICE: asynchronous on the ctx stream, no host
+ * synchronisation inside the call; calls back to back need no synchronize
+ * between them.  Host memory goes through the copy pipeline in the check's
+ * waves; a wave moves the check's bytes plus S bytes back per single-corrected
+ * block and 2 x S (two copies: the shards need not be adjacent) per
+ * pair-corrected block, never the whole wave. */
+int memo_ec_correct_pair_batch(memo_ec_ctx *ctx, int k, int m, int x, size_t S, size_t n,
+                               const uint8_t *have_idx, uint8_t *have,
+                               uint32_t *verdict, int where);
 
 /* Ragged batches: n blocks, each with its own shard size, encoded or verified
  * in one call with no padding byte.

@@ -207,6 +207,22 @@ struct CorrectArgs {
   uint32_t k, x;
 };
 
+// memo_ec_correct_pair_batch, after the check, the single correction and
+// check_pair_kernel: correct_pair_list_kernel (verdict, have_idx -> count,
+// list, bit 24 of the pair words) and gf_correct_pair_kernel (count, list,
+// rows, have -> the two named shards of have).  The layout of count and list
+// and every offset the kernels use: correct_pair_plan.h.
+struct CorrectPairArgs {
+  const uint8_t* have_idx;  // n x (k + x) shard indices, any byte address
+  uint8_t* have;            // n x (k + x) x S, block-major; the named shards are rewritten
+  const uint8_t* rows;      // n x x x k decode rows of the spares over the basis
+  uint32_t* verdict;        // n words of the pair check
+  uint64_t* count;          // list entries, one 64-bit word; zeroed in stream order before the list kernel
+  uint64_t* list;           // up to n entries (correct_pair::make_entry), in no order
+  uint64_t n, S;
+  uint32_t k, x;
+};
+
 struct FillArgs {
   uint8_t* out;
   uint64_t seed, first_block, n, B, stride;
@@ -251,6 +267,9 @@ hipError_t launch_check_pair(const CheckArgs& a, hipStream_t st);
 hipError_t launch_correct_list(const CorrectArgs& a, hipStream_t st);
 // gf_correct_kernel<KC>, KC = mac_kchunk(k, 1)
 hipError_t launch_correct(const CorrectArgs& a, hipStream_t st);
+hipError_t launch_correct_pair_list(const CorrectPairArgs& a, hipStream_t st);
+// gf_correct_pair_kernel<KC>, KC = mac_kchunk(k, 2)
+hipError_t launch_correct_pair(const CorrectPairArgs& a, hipStream_t st);
 hipError_t launch_fill(const FillArgs& a, hipStream_t st);
 hipError_t launch_sha256(const Sha256Args& a, hipStream_t st);
 hipError_t launch_gather(const GatherArgs& a, hipStream_t st);

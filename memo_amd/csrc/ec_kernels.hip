@@ -35,6 +35,7 @@
 
 #include "check_pair_logic.h"
 #include "correct_plan.h"
+#include "correct_pair_plan.h"
 #include "ec_kernels.h"
 
 namespace memo_ec {
@@ -1845,6 +1846,161 @@ __global__ void __launch_bounds__(256) gf_correct_kernel(const CorrectArgs a) {
   }
 }
 
+// ---- memo_ec_correct_pair_batch: the two kernels behind check_pair_kernel.
+
+// The work list of the pair blocks, on correct_list_kernel's scheme: a fixed
+// grid strides over the verdict words, one word per lane.  A word names a pair
+// when it is not MEMO_EC_VERDICT_INVALID and bits 25..31 are nonzero; its
+// positions qa < qb are where have_idx holds the two named shards.  Each wave
+// ballots its pair words, adds their number to the count word with one atomic
+// and writes its entries behind what it got back; each lane sets bit 24 of its
+// own word.  Words the single correction already marked have bits 25..31 zero
+// and are passed over.
+__global__ void __launch_bounds__(256) correct_pair_list_kernel(const CorrectPairArgs a) {
+  const uint32_t kx = a.k + a.x, lane = threadIdx.x % 64;
+  unsigned long long* count = reinterpret_cast<unsigned long long*>(a.count);
+  for (uint64_t base = (uint64_t)blockIdx.x * 256; base < a.n; base += (uint64_t)gridDim.x * 256) {
+    const uint64_t b = base + threadIdx.x;
+    const uint32_t word = b < a.n ? a.verdict[b] : 0u;
+    uint32_t q1 = kx, q2 = kx;
+    if (correct_pair::names_pair(word)) {
+      const uint32_t s1 = MEMO_EC_VERDICT_SHARD(word), s2 = MEMO_EC_VERDICT_SHARD2(word);
+      const uint8_t* row = a.have_idx + b * kx;
+      for (uint32_t t = 0; t < kx; ++t) {
+        const uint32_t v = row[t];
+        q1 = v == s1 ? t : q1;
+        q2 = v == s2 ? t : q2;
+      }
+    }
+    const bool named = q1 < kx && q2 < kx && q1 != q2;
+    const uint64_t votes = __ballot(named);
+    if (votes == 0) continue;  // uniform over the wave
+    unsigned long long first = 0;
+    if (lane == 0) first = atomicAdd(count, (unsigned long long)__popcll(votes));
+    const uint32_t flo = (uint32_t)__shfl((int)(uint32_t)first, 0);
+    const uint32_t fhi = (uint32_t)__shfl((int)(uint32_t)(first >> 32), 0);
+    if (named) {
+      const uint64_t rank = (uint64_t)__popcll(votes & ((1ull << lane) - 1ull));
+      a.list[(((uint64_t)fhi << 32) | flo) + rank] =
+          correct_pair::make_entry(b, q1 < q2 ? q1 : q2, q1 < q2 ? q2 : q1);
+      a.verdict[b] = word | (1u << 24);
+    }
+  }
+}
+
+// The pair correction: gf_correct_kernel with two output rows.  One 4 KiB tile
+// of one list entry per work item, the items dealt to a fixed grid in
+// contiguous ranges; the count is read from device memory, and a batch without
+// pairs finds 0 and leaves.  Per entry the lanes t < k form column t of the
+// 2 x k coefficients M from the block's decode rows D (every square minor of D
+// is nonzero: the k + x positions are a punctured MDS code), over the input
+// positions of correct_pair_plan.h:
+//   spares ra, rb        M[0] = D[ra], M[1] = D[rb]
+//   basis q, spare r     clean row c, i = 1 / D[c][q]:
+//                        M[0][j] = i D[c][j], M[0][q] = i;
+//                        M[1][j] = D[r][j] ^ D[r][q] M[0][j], M[1][q] = D[r][q] i
+//   basis q1 < q2        clean rows c0 < c1 in slots q1, q2, det = D[c0][q1]
+//                        D[c1][q2] ^ D[c0][q2] D[c1][q1]:
+//                        M[0][j] = (D[c1][q2] D[c0][j] ^ D[c0][q2] D[c1][j]) / det,
+//                        M[0][q1] = D[c1][q2] / det, M[0][q2] = D[c0][q2] / det;
+//                        M[1][j] = (D[c1][q1] D[c0][j] ^ D[c0][q1] D[c1][j]) / det,
+//                        M[1][q1] = D[c1][q1] / det, M[1][q2] = D[c0][q1] / det
+// and build the two rows' product tables in LDS (one set, R = 2), kept across
+// the consecutive tiles of the entry.  Per tile each lane loads its 16-byte
+// column of the k inputs once, runs the MAC's chunk body and stores 16 bytes
+// to each target; lanes past S / 16 neither load nor store.  Neither target
+// is read, and no other byte of `have` is written.
+template <int KC>
+__global__ void __launch_bounds__(256) gf_correct_pair_kernel(const CorrectPairArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_gf[kGfDwords];
+  __shared__ __attribute__((aligned(16))) uint32_t s_tab[10 * MEMO_EC_MAX_K];  // q: 4 dwords a slot; lo: 1
+  const uint64_t tpb = correct::tiles_per_block(a.S);
+  const uint64_t total = correct::work_items(*reinterpret_cast<const unsigned long long*>(a.count), tpb);
+  const correct::ItemRange mine = correct::wg_items(total, gridDim.x, blockIdx.x);
+  if (mine.first >= mine.end) return;
+  const uint8_t* lg = reinterpret_cast<const uint8_t*>(s_gf);
+  const uint8_t* ex = lg + 256;
+  const uint32_t k = a.k, kpad = (k + KC - 1) / KC * KC, t = threadIdx.x;
+  MacSeg sg{};
+  sg.lo_dw = 8 * MEMO_EC_MAX_K;
+  TabRef<true> tab;
+  tab.q = s_tab;
+  tab.l = s_tab + sg.lo_dw;
+  stage_gf(s_gf);
+  uint64_t cur = ~0ull;
+  for (uint64_t w = mine.first; w < mine.end; ++w) {
+    const correct::Item it = correct::item_of(w, tpb);
+    const uint64_t e = a.list[it.entry];
+    const uint64_t b = correct_pair::entry_block(e);
+    const uint32_t qa = correct_pair::entry_qa(e), qb = correct_pair::entry_qb(e);
+    if (it.entry != cur) {  // uniform over the workgroup
+      __syncthreads();  // s_gf staged; the previous entry's images all read
+      if (t < kpad) {
+        uint32_t c0 = 0, c1 = 0;
+        if (t < k) {
+          if (qa >= k) {  // two spares
+            c0 = a.rows[correct_pair::row_off(b, correct_pair::spare_row(0, qa, qb, k), k, a.x) + t];
+            c1 = a.rows[correct_pair::row_off(b, correct_pair::spare_row(1, qa, qb, k), k, a.x) + t];
+          } else if (qb >= k) {  // a basis shard and a spare
+            const uint8_t* rc = a.rows + correct_pair::row_off(b, correct_pair::clean_row(0, qa, qb, k), k, a.x);
+            const uint8_t* rr = a.rows + correct_pair::row_off(b, correct_pair::spare_row(1, qa, qb, k), k, a.x);
+            const uint32_t inv = ex[255u - lg[rc[qa]]], rq = rr[qa];
+            c0 = t == qa ? inv : gf_mul_t(lg, ex, inv, rc[t]);
+            c1 = t == qa ? gf_mul_t(lg, ex, rq, inv) : rr[t] ^ gf_mul_t(lg, ex, rq, c0);
+          } else {  // two basis shards
+            const uint8_t* r0 = a.rows + correct_pair::row_off(b, correct_pair::clean_row(0, qa, qb, k), k, a.x);
+            const uint8_t* r1 = a.rows + correct_pair::row_off(b, correct_pair::clean_row(1, qa, qb, k), k, a.x);
+            const uint32_t d00 = r0[qa], d01 = r0[qb], d10 = r1[qa], d11 = r1[qb];
+            const uint32_t det = gf_mul_t(lg, ex, d00, d11) ^ gf_mul_t(lg, ex, d01, d10);
+            const uint32_t idet = ex[255u - lg[det]];
+            uint32_t n0, n1;
+            if (t == qa) {
+              n0 = d11;
+              n1 = d10;
+            } else if (t == qb) {
+              n0 = d01;
+              n1 = d00;
+            } else {
+              const uint32_t u0 = r0[t], u1 = r1[t];
+              n0 = gf_mul_t(lg, ex, d11, u0) ^ gf_mul_t(lg, ex, d01, u1);
+              n1 = gf_mul_t(lg, ex, d10, u0) ^ gf_mul_t(lg, ex, d00, u1);
+            }
+            c0 = gf_mul_t(lg, ex, idet, n0);
+            c1 = gf_mul_t(lg, ex, idet, n1);
+          }
+        }
+        uint4 qv;
+        uint32_t lo;
+        coef_image(c0, qv, lo);
+        put_image(s_tab, sg, 2 * kpad, t, qv, lo);
+        coef_image(c1, qv, lo);
+        put_image(s_tab, sg, 2 * kpad, kpad + t, qv, lo);
+      }
+      __syncthreads();
+      cur = it.entry;
+    }
+    const uint64_t col = correct::col_off(it.tile, t);
+    const bool active = col < a.S;
+    uint32_t acc[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+    for (uint32_t j0 = 0; j0 < k; j0 += KC) {
+      uint4 d[KC];
+#pragma unroll
+      for (int g = 0; g < KC; ++g) {
+        d[g] = make_uint4(0u, 0u, 0u, 0u);
+        if (active && j0 + g < k)
+          d[g] = ld16<MAC_NT>(a.have + correct_pair::input_off(b, j0 + g, qa, qb, k, a.x, a.S) + col);
+      }
+      mac_chunk<KC, 2, true>(acc, d, tab, kpad, j0);
+    }
+    if (active) {
+      st16<MAC_NT>(a.have + correct_pair::target_off(b, 0, qa, qb, k, a.x, a.S) + col,
+                   make_uint4(acc[0][0], acc[0][1], acc[0][2], acc[0][3]));
+      st16<MAC_NT>(a.have + correct_pair::target_off(b, 1, qa, qb, k, a.x, a.S) + col,
+                   make_uint4(acc[1][0], acc[1][1], acc[1][2], acc[1][3]));
+    }
+  }
+}
+
 // ---- Ragged encode and verify: mac_tile with the ragged locate, one span
 // per launch, under names of their own (as gf_mac_images_kernel) so the
 // uniform kernels' code is not disturbed.
@@ -3122,6 +3278,34 @@ hipError_t launch_correct(const CorrectArgs& a, hipStream_t st) {
     case 12: return launch_correct_kc<12>(a, grid, st);
     case 14: return launch_correct_kc<14>(a, grid, st);
     case 16: return launch_correct_kc<16>(a, grid, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_correct_pair_list(const CorrectPairArgs& a, hipStream_t st) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(correct_pair_list_kernel, dim3(correct_pair::list_grid_for(a.n)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// gf_correct_pair_kernel over the shard chunks the MAC is compiled for, R = 2.
+template <int KC>
+static hipError_t launch_correct_pair_kc(const CorrectPairArgs& a, uint32_t grid, hipStream_t st) {
+  hipLaunchKernelGGL(gf_correct_pair_kernel<KC>, dim3(grid), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_correct_pair(const CorrectPairArgs& a, hipStream_t st) {
+  const uint32_t grid = correct_pair::grid_for(a.n, a.S);
+  if (grid == 0) return hipSuccess;
+  switch (mac_kchunk((int)a.k, 2)) {
+    case 2: return launch_correct_pair_kc<2>(a, grid, st);
+    case 3: return launch_correct_pair_kc<3>(a, grid, st);
+    case 4: return launch_correct_pair_kc<4>(a, grid, st);
+    case 6: return launch_correct_pair_kc<6>(a, grid, st);
+    case 10: return launch_correct_pair_kc<10>(a, grid, st);
+    case 12: return launch_correct_pair_kc<12>(a, grid, st);
+    case 14: return launch_correct_pair_kc<14>(a, grid, st);
+    case 16: return launch_correct_pair_kc<16>(a, grid, st);
     default: return hipErrorInvalidValue;
   }
 }

@@ -21,6 +21,7 @@
 #include "../../include/memo_ec.h"
 #include "check_plan.h"
 #include "correct_plan.h"
+#include "correct_pair_plan.h"
 #include "ec_kernels.h"
 #include "ragged_plan.h"
 
@@ -693,6 +694,26 @@ int verify_device(memo_ec_ctx* ctx, int k, int m, size_t S, size_t n, const uint
 DecodeArgs decode_args(const memo_ec_ctx* c, int k, int m, int e, size_t n, const uint8_t* surv_idx,
                        const uint8_t* lost_idx, uint8_t* rows, uint32_t* status, const uint32_t* lw0);
 
+// The arguments of the check's kernels over `scratch` (check::scratch_layout):
+// check_device's, and memo_ec_correct_pair_batch's for check_pair_kernel.
+CheckArgs check_args(int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx, const uint8_t* have,
+                     uint32_t* verdict, uint8_t* scratch) {
+  const check::Scratch lay = check::scratch_layout(n, (unsigned)k, (unsigned)x);
+  CheckArgs a{};
+  a.have_idx = have_idx;
+  a.have = have;
+  a.basis = S ? scratch + lay.basis : nullptr;
+  a.spares = S ? scratch + lay.spares : nullptr;
+  a.rows = S ? scratch + lay.rows : nullptr;
+  a.verdict = verdict;
+  a.n = n;
+  a.S = S;
+  a.k = (uint32_t)k;
+  a.m = (uint32_t)m;
+  a.x = (uint32_t)x;
+  return a;
+}
+
 // Device-resident check of k + x shards in hand on stream st, over `scratch`
 // (check::scratch_layout(n, k, x).total bytes, 256-byte aligned): the prepare
 // kernel (every verdict word written, have_idx split), the decode rows of
@@ -707,18 +728,7 @@ int check_device(memo_ec_ctx* ctx, int k, int m, int x, size_t S, size_t n, cons
                  const uint8_t* have, uint32_t* verdict, uint8_t* scratch, hipStream_t st,
                  bool pair = false) {
   const check::Scratch lay = check::scratch_layout(n, (unsigned)k, (unsigned)x);
-  CheckArgs a{};
-  a.have_idx = have_idx;
-  a.have = have;
-  a.basis = S ? scratch + lay.basis : nullptr;
-  a.spares = S ? scratch + lay.spares : nullptr;
-  a.rows = S ? scratch + lay.rows : nullptr;
-  a.verdict = verdict;
-  a.n = n;
-  a.S = S;
-  a.k = (uint32_t)k;
-  a.m = (uint32_t)m;
-  a.x = (uint32_t)x;
+  const CheckArgs a = check_args(k, m, x, S, n, have_idx, have, verdict, scratch);
   HIPCHK(launch_check_prepare(a, st));
   if (S == 0) return MEMO_EC_OK;
   uint8_t* rows = scratch + lay.rows;
@@ -769,6 +779,38 @@ int correct_device(memo_ec_ctx* ctx, int k, int m, int x, size_t S, size_t n, co
   HIPCHK(hipMemsetAsync(a.count, 0, sizeof(uint64_t), st));
   HIPCHK(launch_correct_list(a, st));
   return hip_rc(launch_correct(a, st));
+}
+
+// Device-resident check-and-mend of one or two wrong shards on stream st, over
+// `scratch` (correct_pair::scratch_layout(n, k, x).total bytes, 256-byte
+// aligned, correct_device's scratch at its start): correct_device first -- the
+// single correction's list kernel takes every word that names a shard, and a
+// pair word's shard field names one, so the singles are listed and marked
+// before any pair word exists --, then check_pair_kernel over the words still
+// unlocated (it passes over the corrected singles), the second count word
+// zeroed, the list of the pair blocks and the pair correction over it, all in
+// stream order with no host synchronisation.  x <= 2 or S == 0 names no pair:
+// the call is correct_device.
+int correct_pair_device(memo_ec_ctx* ctx, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                        uint8_t* have, uint32_t* verdict, uint8_t* scratch, hipStream_t st) {
+  if (int rc = correct_device(ctx, k, m, x, S, n, have_idx, have, verdict, scratch, st)) return rc;
+  if (S == 0 || x < 3) return MEMO_EC_OK;
+  HIPCHK(launch_check_pair(check_args(k, m, x, S, n, have_idx, have, verdict, scratch), st));
+  const correct_pair::Scratch lay = correct_pair::scratch_layout(n, (unsigned)k, (unsigned)x);
+  CorrectPairArgs a{};
+  a.have_idx = have_idx;
+  a.have = have;
+  a.rows = scratch + lay.one.chk.rows;
+  a.verdict = verdict;
+  a.count = reinterpret_cast<uint64_t*>(scratch + lay.count);
+  a.list = reinterpret_cast<uint64_t*>(scratch + lay.list);
+  a.n = n;
+  a.S = S;
+  a.k = (uint32_t)k;
+  a.x = (uint32_t)x;
+  HIPCHK(hipMemsetAsync(a.count, 0, sizeof(uint64_t), st));
+  HIPCHK(launch_correct_pair_list(a, st));
+  return hip_rc(launch_correct_pair(a, st));
 }
 
 // ---- Ragged batches (memo_ec_encode_ragged / memo_ec_verify_ragged).
@@ -1303,12 +1345,14 @@ int check_host(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const ui
 }
 
 // Host-memory check-and-mend: check_host's waves and copies, the wave's
-// kernels being correct_device's.  Once a wave's verdict words have arrived,
-// each corrected block's mended shard (S bytes) is copied from the wave's
+// kernels being correct_device's, or with `pair` (memo_ec_correct_pair_batch)
+// correct_pair_device's.  Once a wave's verdict words have arrived, each
+// corrected block's mended shard (S bytes) -- both shards of a pair-corrected
+// block, in two copies: they need not be adjacent -- goes from the wave's
 // device slot to its place in the caller's `have`, before the slot is reused:
-// a wave moves the check's bytes plus S per corrected block, never all of it.
+// a wave moves the check's bytes plus S per mended shard, never all of it.
 int correct_host(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
-                 uint8_t* have, uint32_t* verdict, bool pinned) {
+                 uint8_t* have, uint32_t* verdict, bool pinned, bool pair) {
   const size_t kx = (size_t)(k + x);
   const std::vector<ragged::Range> waves = call_waves(c, false, n, (uint64_t)kx, [S](size_t) { return S; });
   stage::Plan pl(waves.size(), 3 * waves.size());
@@ -1320,14 +1364,15 @@ int correct_host(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const 
     pl.add(have_idx + w.b0 * kx, cnt * kx, stage::kIn);
     pl.add(verdict + o.verdict, cnt * sizeof(uint32_t), stage::kOut);
     pl.end_wave();
-    scratch = std::max(scratch, correct::scratch_layout(cnt, (unsigned)k, (unsigned)x).total);
+    scratch = std::max(scratch, pair ? correct_pair::scratch_layout(cnt, (unsigned)k, (unsigned)x).total
+                                     : correct::scratch_layout(cnt, (unsigned)k, (unsigned)x).total);
   }
   if (int rc = wait_device_rebuilds(c)) return rc;
   return run_staged(
       c, pl, pinned, false, false, scratch,
       [&](size_t w, const StageView& v, hipStream_t st) {
-        return correct_device(c, k, m, x, S, waves[w].b1 - waves[w].b0, v(1), v(0),
-                              reinterpret_cast<uint32_t*>(v(2)), v.scratch, st);
+        return (pair ? correct_pair_device : correct_device)(c, k, m, x, S, waves[w].b1 - waves[w].b0, v(1), v(0),
+                                                             reinterpret_cast<uint32_t*>(v(2)), v.scratch, st);
       },
       [&](size_t w, uint8_t* dslot, hipStream_t st) -> int {
         if (S == 0 || x < 2) return MEMO_EC_OK;
@@ -1336,14 +1381,16 @@ int correct_host(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const 
         for (size_t b = waves[w].b0; b < waves[w].b1; ++b) {
           const uint32_t word = verdict[b];
           if (word == MEMO_EC_VERDICT_INVALID || !MEMO_EC_VERDICT_CORRECTED(word)) continue;
+          const bool two = pair && MEMO_EC_VERDICT_HAS_PAIR(word);
           const uint8_t* row = have_idx + b * kx;
           for (uint32_t q = 0; q < kx; ++q) {
-            if (row[q] != MEMO_EC_VERDICT_SHARD(word)) continue;
+            if (row[q] != MEMO_EC_VERDICT_SHARD(word) && !(two && row[q] == MEMO_EC_VERDICT_SHARD2(word)))
+              continue;
             HIPCHK(hipMemcpyAsync(have + correct::shard_off(b, q, (uint32_t)k, (uint32_t)x, S),
                                   dhave + correct::shard_off(b - waves[w].b0, q, (uint32_t)k, (uint32_t)x, S),
                                   S, hipMemcpyDeviceToHost, st));
             any = true;
-            break;
+            if (!two) break;
           }
         }
         if (any) HIPCHK(hipStreamSynchronize(st));
@@ -2142,9 +2189,14 @@ int memo_ec_verify_batch(memo_ec_ctx* c, int k, int m, size_t S, size_t n, const
                      });
 }
 
-// memo_ec_check_batch and memo_ec_check_pair_batch (`pair`): one contract.
-static int check_call(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
-                      const uint8_t* have, uint32_t* verdict, int where, bool pair) {
+// The argument checks the check family shares (memo_ec_check_batch,
+// memo_ec_check_pair_batch, memo_ec_correct_batch,
+// memo_ec_correct_pair_batch), in one order, before anything is enqueued.
+// *run is set when the call has work to do; an empty call returns MEMO_EC_OK
+// with *run false.
+static int family_args(const memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                       const uint8_t* have, const uint32_t* verdict, int where, bool* run) {
+  *run = false;
   if (!c) return MEMO_EC_EINVAL;
   if (int rc = check_km(k, m)) return rc;
   if (x < 0 || x > m) return MEMO_EC_EINVAL;
@@ -2154,6 +2206,15 @@ static int check_call(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, c
   if ((S && shard_misaligned(where, have)) || misaligned(verdict, 4)) return MEMO_EC_EINVAL;
   // the index rows count too: with S == 0 they are all the call moves
   if (S >= kMaxShard || too_big(n, (size_t)(k + x) * std::max<size_t>(S, 1))) return MEMO_EC_ERANGE;
+  *run = true;
+  return MEMO_EC_OK;
+}
+
+// memo_ec_check_batch and memo_ec_check_pair_batch (`pair`): one contract.
+static int check_call(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                      const uint8_t* have, uint32_t* verdict, int where, bool pair) {
+  bool run;
+  if (int rc = family_args(c, k, m, x, S, n, have_idx, have, verdict, where, &run); rc || !run) return rc;
   DeviceGuard g(c->device);
   if (where != MEMO_EC_DEVICE)
     return check_host(c, k, m, x, S, n, have_idx, have, verdict, where == MEMO_EC_HOST_PINNED, pair);
@@ -2175,26 +2236,33 @@ int memo_ec_check_pair_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size
   return check_call(c, k, m, x, S, n, have_idx, have, verdict, where, true);
 }
 
-int memo_ec_correct_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
-                          uint8_t* have, uint32_t* verdict, int where) {
-  // the argument checks of memo_ec_check_batch, in its order
-  if (!c) return MEMO_EC_EINVAL;
-  if (int rc = check_km(k, m)) return rc;
-  if (x < 0 || x > m) return MEMO_EC_EINVAL;
-  if (where != MEMO_EC_DEVICE && where != MEMO_EC_HOST && where != MEMO_EC_HOST_PINNED) return MEMO_EC_EINVAL;
-  if (x == 0 || n == 0) return MEMO_EC_OK;
-  if (S % 64 != 0 || !have_idx || !verdict || (S && !have)) return MEMO_EC_EINVAL;
-  if ((S && shard_misaligned(where, have)) || misaligned(verdict, 4)) return MEMO_EC_EINVAL;
-  if (S >= kMaxShard || too_big(n, (size_t)(k + x) * std::max<size_t>(S, 1))) return MEMO_EC_ERANGE;
+// memo_ec_correct_batch and memo_ec_correct_pair_batch (`pair`): one contract.
+static int correct_call(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                        uint8_t* have, uint32_t* verdict, int where, bool pair) {
+  bool run;
+  if (int rc = family_args(c, k, m, x, S, n, have_idx, have, verdict, where, &run); rc || !run) return rc;
   DeviceGuard g(c->device);
   if (where != MEMO_EC_DEVICE)
-    return correct_host(c, k, m, x, S, n, have_idx, have, verdict, where == MEMO_EC_HOST_PINNED);
-  if (int rc = ensure_tabs(c, S ? correct::scratch_layout(n, (unsigned)k, (unsigned)x).total : 0)) return rc;
-  if (int rc = correct_device(c, k, m, x, S, n, have_idx, have, verdict, reinterpret_cast<uint8_t*>(c->d_tabs),
-                              c->stream))
+    return correct_host(c, k, m, x, S, n, have_idx, have, verdict, where == MEMO_EC_HOST_PINNED, pair);
+  const size_t scratch = !S ? 0
+                         : pair ? correct_pair::scratch_layout(n, (unsigned)k, (unsigned)x).total
+                                : correct::scratch_layout(n, (unsigned)k, (unsigned)x).total;
+  if (int rc = ensure_tabs(c, scratch)) return rc;
+  if (int rc = (pair ? correct_pair_device : correct_device)(c, k, m, x, S, n, have_idx, have, verdict,
+                                                             reinterpret_cast<uint8_t*>(c->d_tabs), c->stream))
     return rc;
   // marks the scratch busy until the call is done (host calls check it)
   return S ? hip_rc(hipEventRecord(c->ev_order, c->stream)) : MEMO_EC_OK;
+}
+
+int memo_ec_correct_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n, const uint8_t* have_idx,
+                          uint8_t* have, uint32_t* verdict, int where) {
+  return correct_call(c, k, m, x, S, n, have_idx, have, verdict, where, false);
+}
+
+int memo_ec_correct_pair_batch(memo_ec_ctx* c, int k, int m, int x, size_t S, size_t n,
+                               const uint8_t* have_idx, uint8_t* have, uint32_t* verdict, int where) {
+  return correct_call(c, k, m, x, S, n, have_idx, have, verdict, where, true);
 }
 
 // The ragged calls' argument checks, all on the host before anything is

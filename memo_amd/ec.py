@@ -67,6 +67,7 @@ BUILD_SOURCES = [os.path.join(_ROOT, "include", "memo_ec.h"),
                  os.path.join(_HERE, "csrc", "check_plan.h"),
                  os.path.join(_HERE, "csrc", "correct_plan.h"),
                  os.path.join(_HERE, "csrc", "check_pair_logic.h"),
+                 os.path.join(_HERE, "csrc", "correct_pair_plan.h"),
                  os.path.join(_HERE, "csrc", "ec_kernels.hip"),
                  os.path.join(_HERE, "csrc", "memo_ec.cpp")]
 
@@ -85,6 +86,7 @@ EXPORTS = [
     "memo_ec_device_identity", "memo_ec_stream_probe", "memo_ec_verify_batch",
     "memo_ec_encode_ragged", "memo_ec_verify_ragged", "memo_ec_rebuild_ragged",
     "memo_ec_check_batch", "memo_ec_correct_batch", "memo_ec_check_pair_batch",
+    "memo_ec_correct_pair_batch",
 ]
 
 # memo_ec_verify_batch verdict words: MEMO_EC_VERDICT_UNLOCATED of the header.
@@ -200,6 +202,9 @@ def _lib():
         if hasattr(L, "memo_ec_check_pair_batch"):
             L.memo_ec_check_pair_batch.argtypes = [ctypes.c_void_p, c_int, c_int, c_int, _sz, _sz, _u8p,
                                                    _u8p, ctypes.c_void_p, c_int]
+        if hasattr(L, "memo_ec_correct_pair_batch"):
+            L.memo_ec_correct_pair_batch.argtypes = [ctypes.c_void_p, c_int, c_int, c_int, _sz, _sz, _u8p,
+                                                     _u8p, ctypes.c_void_p, c_int]
         _LIB = L
     return _LIB
 
@@ -502,9 +507,23 @@ class Codec:
                                                vp or None, where), "check_pair")
         return verdict
 
+    def correct_pair(self, k, m, have_idx, have, verdict=None, x=None, S=None, n=None):
+        """memo_ec_correct_pair_batch: check_pair(), and every block with one
+        or two wrong shards mended in `have` on the device: a single-located
+        block as correct() does it, a pair block by the rebuild of its two
+        named shards from k other positions (correct_pair_ref.input_positions).
+        A mended block's word has bit 24 set (verdict_corrected); a pair word
+        keeps its two indices (split_verdict_pair).  Arguments as for check();
+        `have` is written.  Best explanation, not proof: check the mended
+        block against its hash."""
+        x, S, n, ip, hp, vp, where, verdict = self._check_args(k, m, have_idx, have, verdict, x, S, n)
+        _check(_lib().memo_ec_correct_pair_batch(self._ctx, k, m, x, S, n, ip or None, hp or None,
+                                                 vp or None, where), "correct_pair")
+        return verdict
+
     @staticmethod
     def _check_args(k, m, have_idx, have, verdict, x, S, n):
-        """The argument checks of check(), correct() and check_pair():
+        """The argument checks of check(), correct(), check_pair() and correct_pair():
         (x, S, n, have_idx pointer, have pointer, verdict pointer, where, verdict)."""
         if x is None:
             if len(have_idx.shape) != 2:
